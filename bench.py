@@ -6,9 +6,16 @@ CoM / stance states (SURVEY 8(d) generator), inputs already resident in HBM.  De
 BASELINE.json configs[1] (B = 4096 per GPU, horizon 10, double support).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]            the driver's contract
+    python bench.py ... --dump-outputs DIR                          also write the last timed step's results to DIR/<name>.npy
+    python bench.py ... --full                                      also every secondary record and check (below)
     python bench.py --config {2,3,4,5}                              another BASELINE config (own roofline line)
     python bench.py --config {6,7}                                  the long-horizon extensions h = 32 / 40 (stage-structured kernels)
     python bench.py --gpus 8 --config 4 --scaling strong            ONE 65536 batch sharded N ways
+
+A plain run sets up, warms up, times exactly `--steps` steps once, writes the outputs if asked and prints the line.  `--full`
+adds what the headline figure does not need: below 100 steps the timed region repeated five times (the median one reported),
+the `strong` record at N > 1 (weak mode), the bit-exact check of a strong-scaling gather, two batches in flight, ordered
+dispatch, the host-pointer rates, the CPU baseline and the parity of the timed batch against the oracle.
 
 --gpus N > 1 works with or without a launcher: under torch.distributed.run (RANK / WORLD_SIZE in the
 environment) this process is one rank; started bare, it spawns the N ranks itself -- before torch or HIP is
@@ -21,8 +28,8 @@ What a multi-GPU step contains (instances are independent, SURVEY 8(e): no excha
          of step k is asynchronous and overlaps the solve of step k + 1 (two output buffers), as a production
          loop would run it; every gather is complete before the timed region ends.
   strong ONE seeded batch of `--total` instances; per step: RCCL broadcast of the ~0.7 KB parameter block,
-         every rank solves its contiguous shard, all_gather of the controls; afterwards rank 0 solves the
-         whole batch alone and the gathered controls must equal that bit for bit.
+         every rank solves its contiguous shard, all_gather of the controls; afterwards (--full) rank 0 solves
+         the whole batch alone and the gathered controls must equal that bit for bit.
 The timed region is bracketed by barrier + synchronize on both sides; the slowest rank's time counts.
 
 Extra objects on the JSON line:
@@ -30,7 +37,7 @@ Extra objects on the JSON line:
                 measured with HIP events around every launch on the launch stream (DESIGN.md section 6);
                 two counts: SURVEY 8(d)'s dense condensed-ADMM formula (`achieved`) and the flops of the
                 algorithm actually run, symmetric work counted once (`achieved_minimal`).
-  cpu_baseline  the reference-style CPU path (dense np.kron assembly as REF:203-286 + a plain fp64 interior
+  cpu_baseline  (--full) the reference-style CPU path (dense np.kron assembly as REF:203-286 + a plain fp64 interior
                 point solve, oracle/bmpc_oracle.py) on a bounded sample of the same workload: single-core
                 latency split into assembly / solve, and the all-core rate (N = 1, rank 0 only).
 """
@@ -51,6 +58,7 @@ if ROOT not in sys.path:
 MAX_CPU_WORKERS = 16
 PEAK_FP32_TFLOPS = 157.3          # MI355X fp32 vector = fp32 matrix peak (MI355X_MICROARCH.md)
 PEAK_FP64_TFLOPS = 78.6           # MI355X fp64 vector peak (AMD spec sheet: half the fp32 vector rate; the guide lists no fp64 figure)
+DUMP_CAP_BYTES = 64 << 20         # --dump-outputs: everything written, the row indices of a sample included
 
 
 def parse_args(argv=None):
@@ -67,20 +75,29 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="weak: instances per GPU per step (default 4096)")
     ap.add_argument("--total", type=int, default=None, help="strong: instances in the one global batch (default 65536)")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: leave the results on their ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary records and checks (repeated regions, `strong` record, gather check, two batches "
+                         "in flight, ordered dispatch, host-pointer rates, CPU baseline, parity); a plain run does only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         f"at most {DUMP_CAP_BYTES >> 20} MB (a seeded sample of the instances beyond that)")
     ap.add_argument("--no-strong-record", action="store_true",
-                    help="N > 1, weak mode: skip the extra strong-scaling measurement of config 4 (the `strong` sub-record)")
+                    help="--full, N > 1, weak mode: skip the extra strong-scaling measurement of config 4 (the `strong` sub-record)")
     ap.add_argument("--cpu-sample", type=int, default=None,
-                    help="instances for the all-core CPU baseline and the in-run parity (0 = skip; default: the whole batch "
-                         "at h = 10, i.e. ~4 s on 16 cores, 256 otherwise)")
+                    help="--full: instances for the all-core CPU baseline and the in-run parity (0 = skip; default: the whole "
+                         "batch at h = 10, i.e. ~4 s on 16 cores, 256 otherwise)")
     ap.add_argument("--skip-host-path", action="store_true",
-                    help="do not measure the host-pointer (PCIe-inclusive) rate: under rocprofv3 its chunked launches would be "
-                         "averaged into the kernel's statistics (tools/profile_round.sh)")
+                    help="--full: do not measure the host-pointer (PCIe-inclusive) rate: under rocprofv3 its chunked launches "
+                         "would be averaged into the kernel's statistics (tools/profile_round.sh)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal only: initialise torch.distributed and run the collectives even with one rank")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal only: every rank uses cuda:0 (1-GPU box, use with --backend gloo)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ self-launch
@@ -185,6 +202,26 @@ def hbm_bytes_per_solve(h, x_cmd, mu):
     """SURVEY 8(d) compulsory I/O: x_fb, foot, phase, contact (u8) [+ x_cmd] [+ mu] in; controls, states,
     iters / status / nfactor / residuals out."""
     return 4 * (12 + 6 + 1) + 2 * h + (48 if x_cmd else 0) + (8 * h if mu else 0) + 4 * 25 * h + 20
+
+
+# ------------------------------------------------------------------------------------------ --dump-outputs
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES):
+    """Write each array (leading axis = instances) as out_dir/<name>.npy: float32 stays float32, everything else becomes
+    float64 (the integer counters exactly).  If the whole exceeds `cap` bytes, every array keeps the same seeded, sorted
+    sample of its rows -- the same rows for arrays of equal length -- and the indices go to <name>_rows.npy beside it."""
+    import numpy as np
+    arrays = {k: (a if a.dtype == np.float32 else a.astype(np.float64)) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    # a sample keeps the fraction `keep` of every array's rows; its index costs 8 bytes a row; 1 % margin for the .npy headers
+    keep = min(1.0, 0.99 * cap / (total + 8.0 * sum(a.shape[0] for a in arrays.values())))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > cap:
+            n = a.shape[0]
+            rows = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * keep)), replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 # ------------------------------------------------------------------------------------------ CPU baseline
@@ -486,10 +523,10 @@ def run_rank(args):
         # recorded on exactly the stream the kernel runs on
         launch_stream = torch.cuda.Stream(dev)
         # A region of K steps at the headline configuration is 17 ms at the driver's K = 20, and one box differs from the next by
-        # several per cent: below 100 steps the bracketed region of EXACTLY K steps is therefore run
-        # `repeats` = 5 times back to back and the line is the MEDIAN repeat (its wall clock, its kernel events: `ms_per_step`
-        # x `steps` is that region's own time); the spread goes on the line as value_min / value_max.
-        repeats = 5 if steps < 100 else 1
+        # several per cent: under --full, below 100 steps the bracketed region of EXACTLY K steps is therefore
+        # run `repeats` = 5 times back to back and the line is the MEDIAN repeat (its wall clock, its kernel events: `ms_per_step`
+        # x `steps` is that region's own time); the spread goes on the line as value_min / value_max.  A plain run times K steps once.
+        repeats = 5 if (args.full and steps < 100) else 1
         rep_elapsed, rep_kev, rep_gev = [], [], []
         with torch.cuda.stream(launch_stream):
             for _ in range(warmup):
@@ -528,8 +565,17 @@ def run_rank(args):
                    solver=solver, path_used=path_used, path_trial=path_trial, path_arg=path_arg, gather=gather, steps=steps,
                    warmup=warmup, elapsed=elapsed, rep_elapsed=rep_all, kernel_ms=kernel_ms, kernel_ms_ranks=kernel_ms_ranks, gev=gev,
                    iters=o_it.cpu().numpy(), nfac=o_nf.cpu().numpy(), status=o_st.cpu().numpy(), o_u=st["o_u"], gather_check=None)
-        # strong scaling: the gathered controls against the single-GPU solve of the whole batch, bit for bit
-        if gather and strong:
+        # what the last timed step handed its caller (--dump-outputs): this rank's results, and every rank's controls after a gather
+        res["outputs"] = None
+        if args.dump_outputs and rank == 0:
+            res["outputs"] = dict(controls=st["o_u"].cpu().numpy(), states=o_s.cpu().numpy(), residuals=o_rs.cpu().numpy(),
+                                  iters=res["iters"], status=res["status"], nfactor=res["nfac"])
+        if res["outputs"] is not None and gather:
+            res["outputs"]["controls_gathered"] = torch.cat(
+                [st["g_out"][r * per:r * per + (sharding.shard_bounds(total, r, world)[1] - sharding.shard_bounds(total, r, world)[0])]
+                 for r in range(world)]).cpu().numpy()
+        # strong scaling (--full): the gathered controls against the single-GPU solve of the whole batch, bit for bit
+        if gather and strong and args.full:
             fence()
             if rank == 0:
                 tall = dev_inputs(0, total)
@@ -617,10 +663,13 @@ def run_rank(args):
     use_x_cmd, solver, path_used, path_trial, gather = R["use_x_cmd"], R["solver"], R["path_used"], R["path_trial"], R["gather"]
     elapsed, kernel_ms, kernel_ms_ranks, gev, o_u = R["elapsed"], R["kernel_ms"], R["kernel_ms_ranks"], R["gev"], R["o_u"]
     rep_elapsed = R["rep_elapsed"]
-    # N > 1, default (weak) mode: the north_star partition measured in the same run -- ONE 65536 batch of config 4 (mixed gait
-    # schedules) sharded over the ranks, broadcast + solve + all_gather per step, gather checked bit for bit
+    if R["outputs"] is not None:
+        dump_outputs(args.dump_outputs, R["outputs"])
+        _log(f"outputs of the last timed step written to {args.dump_outputs}")
+    # --full, N > 1, default (weak) mode: the north_star partition measured in the same run -- ONE 65536 batch of config 4 (mixed
+    # gait schedules) sharded over the ranks, broadcast + solve + all_gather per step, gather checked bit for bit
     R2 = None
-    if use_dist and not strong and not args.no_gather and not args.no_strong_record:      # (N > 1; one rank under --force-dist)
+    if args.full and use_dist and not strong and not args.no_gather and not args.no_strong_record:   # (N > 1; one rank under --force-dist)
         R2 = timed_run(4, True, "auto", args.steps, args.warmup, total_arg=args.total)
         R2["solver"].close()
 
@@ -666,9 +715,10 @@ def run_rank(args):
             "config": {"workload": f"{cfg['label']}; {what}, inputs resident in HBM",
                        "timed_regions": {"repeats": len(rep_elapsed), "reported": "median" if len(rep_elapsed) > 1 else "the one region",
                                          "ms_per_step_each": [1e3 * t / args.steps for t in rep_elapsed],
-                                         "why": "below 100 steps the bracketed region of exactly `steps` steps is run 5 times back to back "
-                                                "(a 20-step region is 17 ms; boxes differ by several per cent) and `value`, `ms_per_step`, "
-                                                "`roofline.kernel_ms` are those of the median region"},
+                                         "why": "under --full, below 100 steps the bracketed region of exactly `steps` steps is run 5 times "
+                                                "back to back (a 20-step region is 17 ms; boxes differ by several per cent) and `value`, "
+                                                "`ms_per_step`, `roofline.kernel_ms` are those of the median region; a plain run times "
+                                                "one region"},
                        "baseline_config": args.config, "batch_per_gpu": B, "total": total, "horizon": h,
                        "path": path_used, "path_choice": (
                            {"how": "both kernel families timed on this batch before the timed region (ms per launch)", **path_trial}
@@ -745,7 +795,7 @@ def run_rank(args):
                 "mean_iters_rank0": float(R2["iters"].mean()), "not_converged_rank0": int((R2["status"] != 0).sum())}
     if rank == 0 and R["gather_check"]:
         line["config"]["gather_check"] = R["gather_check"]
-    if rank == 0 and args.skip_host_path:
+    if rank == 0 and (args.skip_host_path or not args.full):
         print(json.dumps(line), flush=True)
     elif rank == 0:
         if world == 1:

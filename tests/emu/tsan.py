@@ -45,8 +45,9 @@ def races(stderr):
     return out
 
 
-def run(name="cfg2_standing_h10", n=1):
-    """Returns (stdout, stderr, returncode) of the sanitized emulation of the first n instances of a fixture."""
+def run(name="cfg2_standing_h10", n=1, out=None):
+    """Returns (stdout, stderr, returncode) of the sanitized emulation of the first n instances of a fixture.  The binary and
+    its input go to `out` (default: $BMPC_TSAN_DIR, else a fresh temporary directory)."""
     import biped_mpc_py_amd as bm
     from tests import util
     h, half = util.BATCH_FIXTURES[name]
@@ -55,11 +56,17 @@ def run(name="cfg2_standing_h10", n=1):
     mpc.h = h
     cp = bm.pack_params(mpc, bm.Biped(), half=half)
     mu = d["mu_steps"][:n] if "mu_steps" in d.files and d["mu_steps"].size else None
-    out = os.environ.get("BMPC_TSAN_DIR", "/tmp")
+    if out is None:
+        import tempfile
+        out = os.environ.get("BMPC_TSAN_DIR") or tempfile.mkdtemp(prefix="bmpc_tsan_")
     exe, inp = os.path.join(out, "bmpc_tsan"), os.path.join(out, "bmpc_tsan.in")
     build(exe)
     dump(inp, cp, d["x_fb"][:n], d["foot"][:n], d["contact"][:n], util.phases(d["t"][:n], mpc.dt, h), d["x_cmd"][:n], mu)
-    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 report_signal_unsafe=0 history_size=4 exitcode=0")
+    opts = "halt_on_error=0 report_signal_unsafe=0 history_size=4 exitcode=0"
+    sym = os.path.join(os.path.dirname(CLANG), "llvm-symbolizer")     # file:line in the reports without relying on PATH
+    if os.path.exists(sym):
+        opts += " external_symbolizer_path=" + sym
+    env = dict(os.environ, TSAN_OPTIONS=opts)
     r = subprocess.run([exe, inp], env=env, capture_output=True, text=True)
     return r.stdout, r.stderr, r.returncode
 

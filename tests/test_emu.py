@@ -97,7 +97,7 @@ def test_warm_start_same_optimum_on_cpu():
     print("iterations: warm", o1["iters"][0], "cold", cold1["iters"][0])     # fewer on average, not for every instance
 
 
-def test_no_lds_hand_over_without_a_barrier():
+def test_no_lds_hand_over_without_a_barrier(tmp_path):
     """The emulation under ThreadSanitizer (tests/emu/tsan.py): lanes synchronise only where the GPU does (workgroup
     barrier, pair exchange, wave reduction), so an LDS value handed from one lane to another without an s_barrier in
     between is a data race on the shared-memory image.  The only reports allowed are write/write pairs from ONE source
@@ -106,7 +106,7 @@ def test_no_lds_hand_over_without_a_barrier():
     if not os.path.exists(tsan.CLANG):
         pytest.skip("host clang not available")
     try:
-        out, err, rc = tsan.run("cfg2_standing_h10", 1)
+        out, err, rc = tsan.run("cfg2_standing_h10", 1, out=str(tmp_path))
     except Exception as e:                      # the sanitizer runtime may be missing from a stripped-down image
         pytest.skip(f"sanitized build failed: {e}")
     if "FATAL: ThreadSanitizer" in err:

@@ -711,7 +711,7 @@ def test_bench_two_ranks_strong_scaling():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--config", "4", "--scaling", "strong", "--total", "4099", "--backend", "gloo", "--share-device"],
+                        "--config", "4", "--scaling", "strong", "--total", "4099", "--backend", "gloo", "--share-device", "--full"],
                        env=env, capture_output=True, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = json.loads([x for x in p.stdout.decode().splitlines() if x.startswith("{")][-1])
@@ -722,7 +722,7 @@ def test_bench_two_ranks_strong_scaling():
 
 
 def test_bench_bare_n_gpus_reports_the_north_star_partition_and_proves_its_rank_count():
-    """What the driver runs at N > 1 -- bare `bench.py --gpus N --steps K --warmup W`, nothing else -- must carry, on ONE
+    """`bench.py --gpus N --steps K --warmup W --full` started bare (no launcher) must carry, on ONE
     line: `value` = the weak-scaling number (N = 1 equals BENCH), a `strong` record = the north_star partition (ONE batch of
     config 4 sharded over the ranks, broadcast + solve + all_gather per step, gathered controls bit-identical to the
     single-GPU solve, solves/s), and in `ranks` the world size the PROCESS GROUP reports after init_process_group together
@@ -735,7 +735,7 @@ def test_bench_bare_n_gpus_reports_the_north_star_partition_and_proves_its_rank_
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--total", "8193", "--backend", "gloo", "--share-device"], env=env, capture_output=True, timeout=900)
+                        "--total", "8193", "--backend", "gloo", "--share-device", "--full"], env=env, capture_output=True, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = json.loads([x for x in p.stdout.decode().splitlines() if x.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["config"]["baseline_config"] == 2
@@ -769,7 +769,7 @@ def test_bench_bare_five_ranks_ragged_shards_and_a_killed_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "5", "--steps", "2", "--warmup", "1",
-           "--total", "65539", "--backend", "gloo", "--share-device", "--cpu-sample", "0", "--batch", "1024"]
+           "--total", "65539", "--backend", "gloo", "--share-device", "--cpu-sample", "0", "--batch", "1024", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = json.loads([x for x in p.stdout.decode().splitlines() if x.startswith("{")][-1])
@@ -810,7 +810,7 @@ def test_bench_collectives_over_rccl_single_rank_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "3", "--warmup", "1",
-                        "--total", "8193", "--cpu-sample", "0", "--skip-host-path"], env=env, capture_output=True, timeout=900)
+                        "--total", "8193", "--cpu-sample", "0", "--skip-host-path", "--full"], env=env, capture_output=True, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = json.loads([x for x in p.stdout.decode().splitlines() if x.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["collectives_in_step"] == ["all_gather(controls)"]
@@ -821,7 +821,7 @@ def test_bench_collectives_over_rccl_single_rank_rehearsal():
 
 
 def test_bench_default_line_carries_the_contract_and_the_secondary_records():
-    """The driver's N = 1 run (`python bench.py`, shortened here): the contract's keys, `roofline` and `cpu_baseline`, the parity
+    """The N = 1 run with every secondary record (`python bench.py --full`, shortened here): the contract's keys, `roofline` and `cpu_baseline`, the parity
     of the timed batch, and the two secondary rates -- the host-pointer path and two batches in flight -- each bit-identical to
     the timed device-resident solve."""
     import json
@@ -830,7 +830,7 @@ def test_bench_default_line_carries_the_contract_and_the_secondary_records():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--cpu-sample", "64"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--cpu-sample", "64", "--full"],
                        env=env, capture_output=True, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     out = [x for x in p.stdout.decode().splitlines() if x.strip()]
@@ -850,6 +850,53 @@ def test_bench_default_line_carries_the_contract_and_the_secondary_records():
     assert two["bit_identical_to_one_at_a_time"] and two["streams"] == 2 and two["value"] > 0.9 * line["value"]
     od = line["ordered_dispatch"]                         # (longest first by the previous solve's counts: same results, not slower)
     assert od["bit_identical_to_batch_order"] and od["value"] > 0.95 * line["value"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full): ONE region of exactly `--steps` steps, the contract's keys and none of the --full records;
+    `--dump-outputs` holds the last timed step's results, bit for bit the solve of the same seeded config-2 batch."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    import biped_mpc_py_amd as bm
+    from biped_mpc_py_amd.synth import CONFIGS, synth_batch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    B = 512
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "7", "--warmup", "1", "--batch", str(B),
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    out = [x for x in p.stdout.decode().splitlines() if x.strip()]
+    assert len(out) == 1
+    line = json.loads(out[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 7 and line["config"]["timed_regions"]["repeats"] == 1
+    assert abs(line["value"] - B * 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]
+    for k in ("cpu_baseline", "parity", "value_incl_pcie", "two_batches_in_flight", "ordered_dispatch", "strong"):
+        assert k not in line, k
+    cfg = CONFIGS[2]
+    h = cfg["h"]
+    s = synth_batch(B, h, cfg["seed"], gait=cfg["gait"], **cfg["kw"])
+    mpc = bm.MPC()
+    mpc.h = h
+    dev = torch.device("cuda", 0)
+    solver = bm.BatchSolver(cparams=bm.pack_params(mpc, bm.Biped(), half=s["half"], solver_options=dict(path=0)), device=0, max_batch=B)
+    want = dict(controls=torch.empty((B, h, 12), dtype=torch.float32, device=dev), states=torch.empty((B, h, 13), dtype=torch.float32, device=dev),
+                residuals=torch.empty((B, 2), dtype=torch.float32, device=dev), iters=torch.empty(B, dtype=torch.int32, device=dev),
+                status=torch.empty(B, dtype=torch.int32, device=dev), nfactor=torch.empty(B, dtype=torch.int32, device=dev))
+    solver.solve_device(torch.from_numpy(s["x_fb"].astype(np.float32)).to(dev), torch.from_numpy(s["foot"].astype(np.float32)).to(dev),
+                        torch.from_numpy(np.ascontiguousarray(s["contact"])).to(dev), torch.from_numpy(np.ascontiguousarray(s["phase"])).to(dev),
+                        **want)
+    torch.cuda.synchronize(dev)
+    solver.close()
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in want)
+    for k, t in want.items():
+        got = np.load(tmp_path / (k + ".npy"))
+        assert got.dtype == (np.float32 if t.dtype == torch.float32 else np.float64), k
+        assert np.array_equal(got, t.cpu().numpy().astype(got.dtype)), k
 
 
 @pytest.mark.parametrize("gait", ["standing", "walking"])

@@ -125,6 +125,28 @@ def test_bench_flop_counts_and_bytes():
     assert fl == parts["setup"] + 6.0 * parts["factor"] + 56.0 * parts["iteration"]
 
 
+def test_bench_dump_outputs_dtypes_cap_and_seeded_sample(tmp_path):
+    """`bench.py --dump-outputs`: float32 arrays as they are, the integer counters as float64; above the byte cap every array
+    keeps the same seeded sample of rows (indices beside it), identical from run to run, and the files stay within the cap."""
+    import bench
+    arrays = {"controls": np.arange(4000 * 30, dtype=np.float32).reshape(4000, 30), "iters": np.arange(4000, dtype=np.int32) * 3}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    c, it = np.load(tmp_path / "all" / "controls.npy"), np.load(tmp_path / "all" / "iters.npy")
+    assert c.dtype == np.float32 and np.array_equal(c, arrays["controls"])
+    assert it.dtype == np.float64 and np.array_equal(it, arrays["iters"])
+    assert sorted(os.listdir(tmp_path / "all")) == ["controls.npy", "iters.npy"]
+    cap = 100_000
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, cap=cap)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= cap
+    rows = np.load(tmp_path / "a" / "controls_rows.npy")
+    assert 0 < len(rows) < 4000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "a" / "iters_rows.npy"))
+    for name in ("controls", "iters", "controls_rows", "iters_rows"):
+        assert np.array_equal(np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy")))
+    assert np.array_equal(np.load(tmp_path / "a" / "controls.npy"), arrays["controls"][rows.astype(np.int64)])
+
+
 def test_pack_params_half_defaults_follow_the_horizon():
     """`half` defaults to what bmpc_default_params chose: the reference's 5 at h = 10 (REF:101-105), h / 2 otherwise."""
     import biped_mpc_py_amd as bm

@@ -19,7 +19,7 @@ case "$1" in
     for rep in 1 2 3; do
       for v in "$@"; do
         cp build_tmp/$v.so biped_mpc_py_amd/libbmpc.so
-        python bench.py --steps 30 --warmup 5 --cpu-sample 0 $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-12s' % '$v', '%.4f ms/step kernel %.4f ms iters %.2f max %d' % (d['ms_per_step'], d['roofline']['kernel_ms'], d['config']['mean_iters'], d['config']['max_iters']))"
+        python bench.py --steps 30 --warmup 5 --full --cpu-sample 0 $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-12s' % '$v', '%.4f ms/step kernel %.4f ms iters %.2f max %d' % (d['ms_per_step'], d['roofline']['kernel_ms'], d['config']['mean_iters'], d['config']['max_iters']))"
       done
     done
     ;;
