@@ -113,13 +113,14 @@ def load():
     lib.bmpc_destroy.argtypes = [vp]
     lib.bmpc_set_params.argtypes = [vp, C.POINTER(CParams)]
     lib.bmpc_get_params.argtypes = [vp, C.POINTER(CParams)]
-    ptrs14 = [vp] * 12
-    lib.bmpc_solve_batch.argtypes = [vp, ip] + ptrs14
-    lib.bmpc_solve_batch_f64.argtypes = [vp, ip] + ptrs14
-    lib.bmpc_solve_batch_device.argtypes = [vp, ip] + ptrs14 + [vp]
+    ptrs12 = [vp] * 12
+    lib.bmpc_solve_batch.argtypes = [vp, ip] + ptrs12
+    lib.bmpc_solve_batch_f64.argtypes = [vp, ip] + ptrs12
+    lib.bmpc_solve_batch_device.argtypes = [vp, ip] + ptrs12 + [vp]
     lib.bmpc_synchronize.argtypes = [vp]
     lib.bmpc_host_io.argtypes = [vp, ip, ip, ip, ip, C.POINTER(CHostViews)]
     lib.bmpc_solve_batch_io.argtypes = [vp, ip]
+    lib.bmpc_host_io_generation.argtypes = [vp]
     lib.bmpc_debug_assemble.argtypes = [vp, ip] + [vp] * 10
     lib.bmpc_debug_set_profile.argtypes = [vp, vp]
     lib.bmpc_foot_position_world.argtypes = [vp, ip, vp, vp, vp]

@@ -258,6 +258,31 @@ struct DevBuf {
   void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
 
+// Offsets of the packed arrays of n instances, every array `align`-byte aligned (a power of two).  Inputs: x_fb, foot, phase
+// [, x_cmd] [, mu], contact; outputs: controls [, states] in elements of out_elem bytes (f32 or f64), iters, status, nfactor,
+// residuals.
+struct PackedLayout {
+  size_t i_xfb = 0, i_foot = 0, i_phase = 0, i_xcmd = 0, i_mu = 0, i_con = 0, in_bytes = 0;
+  size_t o_u = 0, o_s = 0, o_it = 0, o_st = 0, o_nf = 0, o_rs = 0, out_bytes = 0;
+};
+PackedLayout packed_layout(size_t n, size_t H, bool x_cmd, bool mu, bool states, size_t align, size_t out_elem) {
+  auto up = [align](size_t v) { return (v + align - 1) & ~(align - 1); };
+  PackedLayout L;
+  L.i_foot = up(L.i_xfb + n * 12 * 4);
+  L.i_phase = up(L.i_foot + n * 6 * 4);
+  L.i_xcmd = up(L.i_phase + n * 4);
+  L.i_mu = up(L.i_xcmd + (x_cmd ? n * 12 * 4 : 0));
+  L.i_con = up(L.i_mu + (mu ? n * H * 2 * 4 : 0));
+  L.in_bytes = up(L.i_con + n * H * 2);
+  L.o_s = up(L.o_u + n * H * 12 * out_elem);
+  L.o_it = up(L.o_s + (states ? n * H * 13 * out_elem : 0));
+  L.o_st = up(L.o_it + n * 4);
+  L.o_nf = up(L.o_st + n * 4);
+  L.o_rs = up(L.o_nf + n * 4);
+  L.out_bytes = up(L.o_rs + n * 2 * 4);
+  return L;
+}
+
 }  // namespace
 
 struct bmpc_handle_s {
@@ -291,11 +316,9 @@ struct bmpc_handle_s {
   DevBuf<double> io_states;         // fp64 states of a batch in HBM, on their way to the I/O block by copy engine
   hipEvent_t cev_in = nullptr;      // the I/O block's inputs have arrived
   int io_gen = 0;                   // moves with every bmpc_host_io call (bmpc_host_io_generation)
-  struct IoLayout {
+  struct IoLayout : PackedLayout {
     int B = 0;
     bool x_cmd = false, mu = false, states = false;
-    size_t i_xfb = 0, i_foot = 0, i_phase = 0, i_xcmd = 0, i_mu = 0, i_con = 0, in_bytes = 0;
-    size_t o_u = 0, o_s = 0, o_it = 0, o_st = 0, o_nf = 0, o_rs = 0, out_bytes = 0;
   } io;
   DevBuf<float> x_fb, foot, x_cmd, mu, controls, states, resid;
   DevBuf<uint8_t> contact;
@@ -326,15 +349,34 @@ namespace {
 // stage-structured kernels (bmpc_stage.hip).
 #define BMPC_DENSE_HORIZONS(X) X(8) X(10) X(12) X(14) X(16) X(18) X(20)
 
-template <int H>
-int launch_h(bmpc_handle hd, int B, const float* x_fb, const float* foot, const uint8_t* contact,
-             const int32_t* phase, const float* x_cmd, const float* mu, float* controls, float* states,
-             int32_t* iters, float* resid, int32_t* status, int32_t* nfactor, const bmpc::DebugOut& dbg,
-             hipStream_t st, const int32_t* order, double* c64, double* s64) {
-  constexpr int NT = bmpc::Dims<H>::NT;
-  bmpc::WarmArgs warm = {nullptr, 0, 0, 0, 1.f, 0, dbg.assemble_only ? nullptr : order, nullptr, c64, s64};
-  if (hd->warm_on && !dbg.assemble_only) {
-    const size_t need = (size_t)B * NT * 6;
+// The buffers of one solve launch, as bmpc_solve_batch_device takes them: device-addressable pointers (on the I/O path some
+// point into mapped page-locked host memory), null where that entry point allows it.  controls64 / states64: fp64 outputs
+// that take the place of controls / states (bmpc::WarmArgs).
+struct SolveIO {
+  const float* x_fb = nullptr;
+  const float* foot = nullptr;
+  const uint8_t* contact = nullptr;
+  const int32_t* phase = nullptr;
+  const float* x_cmd = nullptr;
+  const float* mu = nullptr;
+  float* controls = nullptr;
+  float* states = nullptr;
+  int32_t* iters = nullptr;
+  float* resid = nullptr;
+  int32_t* status = nullptr;
+  int32_t* nfactor = nullptr;
+  double* controls64 = nullptr;
+  double* states64 = nullptr;
+};
+
+// One launch of either kernel family: the warm-start set-up (warm_per_inst doubles of solver state per instance), then
+// `kernel(args...)`, which launches the family's kernel with the parameter list both families share.
+template <typename Kernel>
+int launch_family(bmpc_handle hd, int B, size_t warm_per_inst, const SolveIO& io, const bmpc::DebugOut& dbg,
+                  const int32_t* order, const int32_t* rescue_status, Kernel kernel) {
+  bmpc::WarmArgs warm = {nullptr, 0, 0, 0, 1.f, 0, dbg.assemble_only ? nullptr : order, rescue_status, io.controls64, io.states64};
+  if (hd->warm_on && !dbg.assemble_only && !rescue_status) {   // (a rescue pass starts cold: the stored state is the dense family's)
+    const size_t need = (size_t)B * warm_per_inst;
     if (need > hd->warm.n) hd->warm_valid = false;          // growing the buffer loses the stored state
     HIP_TRY(hd->warm.ensure(need));
     warm.buf = hd->warm.p;
@@ -344,80 +386,61 @@ int launch_h(bmpc_handle hd, int B, const float* x_fb, const float* foot, const 
     warm.theta = hd->warm_theta;
     warm.adapt_start = hd->params.warm_adapt_start;
   }
-  if (dbg.prof)     // diagnostics build of the same body: in-kernel cycle stamps (bmpc_debug_set_profile)
-    hipLaunchKernelGGL((bmpc::solve_kernel_prof<H>), dim3(B), dim3(NT), 0, st, hd->dev, B, x_fb, foot, contact,
-                       phase, x_cmd, mu, controls, states, iters, resid, status, nfactor, dbg, warm);
-  else
-    hipLaunchKernelGGL((bmpc::solve_kernel<H>), dim3(B), dim3(NT), 0, st, hd->dev, B, x_fb, foot, contact,
-                       phase, x_cmd, mu, controls, states, iters, resid, status, nfactor, dbg, warm);
+  kernel(hd->dev, B, io.x_fb, io.foot, io.contact, io.phase, io.x_cmd, io.mu, io.controls, io.states, io.iters, io.resid,
+         io.status, io.nfactor, dbg, warm);
   HIP_TRY(hipGetLastError());
   if (warm.buf) { hd->warm_valid = true; hd->warm_batch = B; }
   return BMPC_OK;
+}
+
+// (dbg.prof: the diagnostics build of the same body, with in-kernel cycle stamps -- bmpc_debug_set_profile)
+template <int H>
+int launch_h(bmpc_handle hd, int B, const SolveIO& io, const bmpc::DebugOut& dbg, hipStream_t st, const int32_t* order) {
+  constexpr int NT = bmpc::Dims<H>::NT;
+  return launch_family(hd, B, NT * 6, io, dbg, order, nullptr, [&](auto... args) {
+    if (dbg.prof) hipLaunchKernelGGL((bmpc::solve_kernel_prof<H>), dim3(B), dim3(NT), 0, st, args...);
+    else hipLaunchKernelGGL((bmpc::solve_kernel<H>), dim3(B), dim3(NT), 0, st, args...);
+  });
 }
 
 template <int NP, int NW>
-int launch_stage(bmpc_handle hd, int B, const float* x_fb, const float* foot, const uint8_t* contact,
-                 const int32_t* phase, const float* x_cmd, const float* mu, float* controls, float* states,
-                 int32_t* iters, float* resid, int32_t* status, int32_t* nfactor, const bmpc::DebugOut& dbg,
-                 hipStream_t st, const int32_t* order, const int32_t* rescue_status, double* c64, double* s64) {
-  bmpc::WarmArgs warm = {nullptr, 0, 0, 0, 1.f, 0, dbg.assemble_only ? nullptr : order, rescue_status, c64, s64};
-  if (hd->warm_on && !dbg.assemble_only && !rescue_status) {   // (a rescue pass starts cold: the stored state is the dense family's)
-    const size_t need = (size_t)B * (5 * NP * NW) * 12 * 6;  // [B][5 NP NW][12][6] doubles
-    if (need > hd->warm.n) hd->warm_valid = false;
-    HIP_TRY(hd->warm.ensure(need));
-    warm.buf = hd->warm.p;
-    warm.load = (hd->warm_valid && hd->warm_batch == B) ? 1 : 0;
-    warm.store = 1;
-    warm.shift = hd->warm_shift;
-    warm.theta = hd->warm_theta;
-    warm.adapt_start = hd->params.warm_adapt_start;
-  }
-  if (dbg.prof)
-    hipLaunchKernelGGL((bmpc::stage_kernel_prof<NP, NW>), dim3(B), dim3(64 * NW), 0, st, hd->dev, B, x_fb, foot, contact,
-                       phase, x_cmd, mu, controls, states, iters, resid, status, nfactor, dbg, warm);
-  else
-    hipLaunchKernelGGL((bmpc::stage_kernel<NP, NW>), dim3(B), dim3(64 * NW), 0, st, hd->dev, B, x_fb, foot, contact,
-                       phase, x_cmd, mu, controls, states, iters, resid, status, nfactor, dbg, warm);
-  HIP_TRY(hipGetLastError());
-  if (warm.buf) { hd->warm_valid = true; hd->warm_batch = B; }
-  return BMPC_OK;
+int launch_stage(bmpc_handle hd, int B, const SolveIO& io, const bmpc::DebugOut& dbg, hipStream_t st, const int32_t* order,
+                 const int32_t* rescue_status) {
+  return launch_family(hd, B, (5 * NP * NW) * 12 * 6, io, dbg, order, rescue_status, [&](auto... args) {  // [5 NP NW][12][6]
+    if (dbg.prof) hipLaunchKernelGGL((bmpc::stage_kernel_prof<NP, NW>), dim3(B), dim3(64 * NW), 0, st, args...);
+    else hipLaunchKernelGGL((bmpc::stage_kernel<NP, NW>), dim3(B), dim3(64 * NW), 0, st, args...);
+  });
 }
 
-int launch_stage_any(bmpc_handle hd, int B, const float* x_fb, const float* foot, const uint8_t* contact,
-                     const int32_t* phase, const float* x_cmd, const float* mu, float* controls, float* states,
-                     int32_t* iters, float* resid, int32_t* status, int32_t* nfactor, const bmpc::DebugOut& dbg,
-                     hipStream_t st, const int32_t* order, const int32_t* rescue_status, double* c64, double* s64) {
+int launch_stage_any(bmpc_handle hd, int B, const SolveIO& io, const bmpc::DebugOut& dbg, hipStream_t st, const int32_t* order,
+                     const int32_t* rescue_status) {
   // compiled per (steps a lane owns, waves per instance): bmpc::stage_steps_per_lane / stage_waves
   switch (10 * bmpc::stage_waves(hd->dev.h) + bmpc::stage_steps_per_lane(hd->dev.h)) {
-#define BMPC_CASE(NN, WW) case 10 * WW + NN: return launch_stage<NN, WW>(hd, B, x_fb, foot, contact, phase, x_cmd, mu, controls, states, iters, resid, status, nfactor, dbg, st, order, rescue_status, c64, s64);
+#define BMPC_CASE(NN, WW) case 10 * WW + NN: return launch_stage<NN, WW>(hd, B, io, dbg, st, order, rescue_status);
     BMPC_CASE(2, 1) BMPC_CASE(3, 1) BMPC_CASE(4, 1) BMPC_CASE(5, 1) BMPC_CASE(3, 2) BMPC_CASE(4, 2)
 #undef BMPC_CASE
     default: return fail(BMPC_ERR_INVALID, "unsupported horizon h=%d", hd->dev.h);
   }
 }
 
-int launch(bmpc_handle hd, int B, const float* x_fb, const float* foot, const uint8_t* contact,
-           const int32_t* phase, const float* x_cmd, const float* mu, float* controls, float* states,
-           int32_t* iters, float* resid, int32_t* status, int32_t* nfactor, const bmpc::DebugOut& dbg,
-           hipStream_t st, const int32_t* order, double* c64 = nullptr, double* s64 = nullptr) {
+int launch(bmpc_handle hd, int B, SolveIO io, const bmpc::DebugOut& dbg, hipStream_t st, const int32_t* order) {
   const bool dense_views = dbg.assemble_only && (dbg.Gt || dbg.qt);      // Gt, qt only exist on the dense path
   if (hd->path == BMPC_PATH_STAGE && !(dense_views && dense_horizon(hd->dev.h))) {
     if (dense_views) return fail(BMPC_ERR_INVALID, "Gt / qt views exist for h <= 20 only (h=%d never forms them)", hd->dev.h);
-    return launch_stage_any(hd, B, x_fb, foot, contact, phase, x_cmd, mu, controls, states, iters, resid, status, nfactor, dbg, st,
-                            order, nullptr, c64, s64);
+    return launch_stage_any(hd, B, io, dbg, st, order, nullptr);
   }
   // Dense family.  With the rescue pass on, the instances whose status is not 0 afterwards are solved again by the
   // stage-structured kernel of the same horizon (f32 Riccati recursion instead of the f32 explicit inverse: it does not
   // share the dense sweep's rare breakdowns; profiles/r03_soak.txt): one more launch whose workgroups leave at once
   // where the status is 0, no host round trip.
   const bool rescue = hd->rescue_on && !dbg.assemble_only;
-  if (rescue && !status) {
+  if (rescue && !io.status) {
     HIP_TRY(hd->status.ensure((size_t)B));
-    status = hd->status.p;
+    io.status = hd->status.p;
   }
   int rc = BMPC_ERR_INVALID;
   switch (hd->dev.h) {
-#define BMPC_CASE(HH) case HH: rc = launch_h<HH>(hd, B, x_fb, foot, contact, phase, x_cmd, mu, controls, states, iters, resid, status, nfactor, dbg, st, order, c64, s64); break;
+#define BMPC_CASE(HH) case HH: rc = launch_h<HH>(hd, B, io, dbg, st, order); break;
     BMPC_DENSE_HORIZONS(BMPC_CASE)
 #undef BMPC_CASE
     default: return fail(BMPC_ERR_INVALID, "unsupported horizon h=%d", hd->dev.h);
@@ -425,8 +448,7 @@ int launch(bmpc_handle hd, int B, const float* x_fb, const float* foot, const ui
   if (rc != BMPC_OK || !rescue) return rc;
   bmpc::DebugOut quiet = dbg;
   quiet.prof = nullptr;                        // the cycle stamps stay those of the first solve
-  return launch_stage_any(hd, B, x_fb, foot, contact, phase, x_cmd, mu, controls, states, iters, resid, status, nfactor, quiet, st,
-                          order, status, c64, s64);
+  return launch_stage_any(hd, B, io, quiet, st, order, io.status);
 }
 
 // NULL is HIP's null (legacy default) stream, like every hip* call; BMPC_STREAM_OWN the handle's own stream
@@ -435,12 +457,189 @@ hipStream_t pick_stream(bmpc_handle h, void* stream) {
   return static_cast<hipStream_t>(stream);
 }
 
-int check_common(bmpc_handle h, int B, const void* x_fb, const void* foot, const void* contact, const void* phase,
-                 const void* controls) {
+// The handle and batch size every batched entry point checks first: an error code (< 0), BMPC_OK (0) when there is nothing to
+// do (B == 0), or 1 when the call goes on.
+int check_batch(bmpc_handle h, int B) {
   if (!h) return fail(BMPC_ERR_INVALID, "null handle");
   if (B < 0 || B > h->max_batch) return fail(BMPC_ERR_INVALID, "batch %d outside [0, max_batch=%d]", B, h->max_batch);
-  if (B > 0 && (!x_fb || !foot || !contact || !phase || !controls))
+  return B > 0 ? 1 : BMPC_OK;
+}
+
+// check_batch and the arrays a solve cannot do without
+int check_common(bmpc_handle h, int B, const void* x_fb, const void* foot, const void* contact, const void* phase,
+                 const void* controls) {
+  const int rc = check_batch(h, B);
+  if (rc > 0 && (!x_fb || !foot || !contact || !phase || !controls))
     return fail(BMPC_ERR_INVALID, "x_fb, foot, contact, phase and controls must be non-null");
+  return rc;
+}
+
+// one solve launch with the dispatch order given explicitly (roll-outs use their own, the handle's stays untouched)
+// (ev: which of the handle's timing events this launch records -- bit 0: ev0 before it, bit 1: ev1 after it; a batch that goes
+//  out in chunks records ev0 before its first kernel and ev1 after its last, so bmpc_last_kernel_ms spans them all)
+int solve_device_ordered(bmpc_handle h, int B, const SolveIO& io, void* stream, const int32_t* order, int ev = 3) {
+  const void* controls = io.controls64 ? static_cast<const void*>(io.controls64) : static_cast<const void*>(io.controls);
+  if (int rc = check_common(h, B, io.x_fb, io.foot, io.contact, io.phase, controls); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  bmpc::DebugOut dbg = {nullptr, nullptr, nullptr, nullptr, h->prof_dev, 0};
+  if (ev & 1) HIP_TRY(hipEventRecord(h->ev0, st));
+  if (int rc = launch(h, B, io, dbg, st, order); rc != BMPC_OK) return rc;
+  if (ev & 2) { HIP_TRY(hipEventRecord(h->ev1, st)); h->timed = true; }
+  return BMPC_OK;
+}
+
+// ---- the chunked host-pointer entry points (bmpc_solve_batch*, bmpc_solve_batch_io)
+
+// How such a call splits its n instances: contiguous chunks [lo, lo + nb), one per stream priority the device offers (MI355X:
+// three; chunks that share a priority are served round robin and finish together), the later ones smaller: the last chunk's
+// unpacking is the exposed part, and a chunk's unpacking (~1/3 of its solve time) has to fit before the next chunk arrives.
+// Warm start, a dispatch order and the profile buffer index by the instance's position in the whole batch: with any of them
+// set, or `whole`, the batch goes out as one chunk.
+struct ChunkPlan {
+  int n = 1;
+  size_t lo[bmpc_handle_s::HOST_CHUNKS] = {}, nb[bmpc_handle_s::HOST_CHUNKS] = {};
+  int events(int c) const { return (c == 0 ? 1 : 0) | (c == n - 1 ? 2 : 0); }   // solve_device_ordered's ev of chunk c
+};
+ChunkPlan plan_chunks(bmpc_handle h, size_t n, bool whole) {
+  ChunkPlan p;
+  const int k = (whole || h->warm_on || h->order || h->prof_dev) ? 1 : (int)(n / 512);
+  p.n = k < 1 ? 1 : (k > h->host_chunks ? h->host_chunks : k);
+  for (int c = 0; c < p.n; ++c) {
+    p.lo[c] = p.n >= 2 ? (size_t)(n * h->host_cut[c]) : 0;
+    p.nb[c] = (c == p.n - 1 ? n : (size_t)(n * h->host_cut[c + 1])) - p.lo[c];
+  }
+  return p;
+}
+
+// The chunk streams come after what the handle's own stream holds (a device-pointer solve on BMPC_STREAM_OWN, the warm-start
+// state it writes); an idle stream -- the usual case -- is not made to process a marker the chunk streams would then wait for
+// (tens of us).
+hipError_t chunks_after_own_stream(bmpc_handle h, int nchunk) {
+  if (hipStreamQuery(h->stream) == hipSuccess) return hipSuccess;
+  hipError_t e = hipEventRecord(h->cev_own, h->stream);
+  for (int c = 0; c < nchunk && e == hipSuccess; ++c) e = hipStreamWaitEvent(h->cstream[c], h->cev_own, 0);
+  return e;
+}
+
+// An error return of a chunked call first waits for the chunk streams it has queued work on: their copies still read and write
+// the handle's page-locked blocks.
+int bail(bmpc_handle h, int issued, int code) {
+  for (int c = 0; c < issued; ++c) (void)hipStreamSynchronize(h->cstream[c]);
+  return code;
+}
+#define CHUNK_TRY(expr)                                                                                        \
+  do {                                                                                                         \
+    hipError_t e_ = (expr);                                                                                    \
+    if (e_ != hipSuccess) return bail(h, issued, fail(BMPC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_))); \
+  } while (0)
+
+// The arrays of instances lo.. in packed blocks `in` / `out` laid out by L, but for controls and states (f32 or f64)
+SolveIO packed_io(const PackedLayout& L, const char* in, char* out, size_t lo, size_t H, bool x_cmd, bool mu) {
+  SolveIO io;
+  io.x_fb = reinterpret_cast<const float*>(in + L.i_xfb) + lo * 12;
+  io.foot = reinterpret_cast<const float*>(in + L.i_foot) + lo * 6;
+  io.contact = reinterpret_cast<const uint8_t*>(in + L.i_con) + lo * H * 2;
+  io.phase = reinterpret_cast<const int32_t*>(in + L.i_phase) + lo;
+  if (x_cmd) io.x_cmd = reinterpret_cast<const float*>(in + L.i_xcmd) + lo * 12;
+  if (mu) io.mu = reinterpret_cast<const float*>(in + L.i_mu) + lo * H * 2;
+  io.iters = reinterpret_cast<int32_t*>(out + L.o_it) + lo;
+  io.resid = reinterpret_cast<float*>(out + L.o_rs) + lo * 2;
+  io.status = reinterpret_cast<int32_t*>(out + L.o_st) + lo;
+  io.nfactor = reinterpret_cast<int32_t*>(out + L.o_nf) + lo;
+  return io;
+}
+
+// Host pointers in, host pointers out (T = float: bmpc_solve_batch; T = double: bmpc_solve_batch_f64, the dtype the reference
+// returns).  What the reference's callers get (REF:487), so PCIe is part of the path:
+//   * per chunk the inputs are packed into one pinned block and cross in ONE copy; outputs come back one packed block;
+//   * the batch is split into up to HOST_CHUNKS contiguous chunks (plan_chunks), each launched on its own stream (descending
+//     priority: the dispatcher serves chunk 0's workgroups first), followed on that stream by the chunk's device-to-host copy:
+//     the results of chunk c cross PCIe, and are unpacked (widened to fp64) into the caller's pageable arrays by the calling
+//     thread, while chunks c + 1 .. still solve.  Only the last chunk's copy and unpacking are exposed.
+//     (A caller that can take its results in the handle's own page-locked block has no unpacking at all: bmpc_solve_batch_io.)
+// The kernels' arithmetic does not depend on the position in a batch, so the results are bit-identical to a single launch.
+// Ordering: the chunk streams wait for what was queued on the handle's own stream before the call, and the call returns with
+// every chunk complete.
+template <typename T>
+int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact, const int32_t* phase,
+               const float* x_cmd, const float* mu, T* controls, T* states, int32_t* iters, float* residuals, int32_t* status,
+               int32_t* nfactor) {
+  if (int rc = check_common(h, B, x_fb, foot, contact, phase, controls); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t n = (size_t)B, H = (size_t)h->dev.h;
+  const bool timing = h->host_timing;                                 // (diagnostics: where a host-pointer call spends its time)
+  auto now = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const double t_begin = timing ? now() : 0.0;
+  double t_wait = 0, t_unpack = 0, t_last_wait = 0, t_last_unpack = 0;
+  const ChunkPlan plan = plan_chunks(h, n, false);
+  // each chunk's packed blocks (16-byte aligned arrays, f32 outputs), one after the other in pin_in / dev_in and pin_out / dev_out
+  struct Chunk { PackedLayout L; size_t in, out; } ck[bmpc_handle_s::HOST_CHUNKS];
+  size_t in_bytes = 0, out_bytes = 0;
+  for (int c = 0; c < plan.n; ++c) {
+    ck[c] = {packed_layout(plan.nb[c], H, x_cmd, mu, states, 16, 4), in_bytes, out_bytes};
+    in_bytes += ck[c].L.in_bytes;
+    out_bytes += ck[c].L.out_bytes;
+  }
+  HIP_TRY(h->pin_in.ensure(in_bytes));
+  HIP_TRY(h->dev_in.ensure(in_bytes));
+  HIP_TRY(h->pin_out.ensure(out_bytes));
+  HIP_TRY(h->dev_out.ensure(out_bytes));
+  HIP_TRY(chunks_after_own_stream(h, plan.n));
+  int issued = 0;                               // chunks whose work is queued (an error below waits for them before returning)
+  for (int c = 0; c < plan.n; ++c) {
+    const PackedLayout& L = ck[c].L;
+    const size_t lo = plan.lo[c], nb = plan.nb[c];
+    // inputs of this chunk: packed into the pinned block and sent in ONE copy (chunk 0 is on its way while the later
+    // chunks are still being packed)
+    char* pin = h->pin_in.p + ck[c].in;
+    char* din = h->dev_in.p + ck[c].in;
+    std::memcpy(pin + L.i_xfb, x_fb + lo * 12, nb * 12 * 4);
+    std::memcpy(pin + L.i_foot, foot + lo * 6, nb * 6 * 4);
+    std::memcpy(pin + L.i_phase, phase + lo, nb * 4);
+    if (x_cmd) std::memcpy(pin + L.i_xcmd, x_cmd + lo * 12, nb * 12 * 4);
+    if (mu) std::memcpy(pin + L.i_mu, mu + lo * H * 2, nb * H * 2 * 4);
+    std::memcpy(pin + L.i_con, contact + lo * H * 2, nb * H * 2);
+    hipStream_t st = h->cstream[c];
+    issued = c + 1;
+    CHUNK_TRY(hipMemcpyAsync(din, pin, L.in_bytes, hipMemcpyHostToDevice, st));
+    char* dout = h->dev_out.p + ck[c].out;
+    SolveIO io = packed_io(L, din, dout, 0, H, x_cmd, mu);
+    io.controls = reinterpret_cast<float*>(dout + L.o_u);
+    if (states) io.states = reinterpret_cast<float*>(dout + L.o_s);
+    if (int rc = solve_device_ordered(h, (int)nb, io, st, h->order, plan.events(c)); rc != BMPC_OK) return bail(h, issued, rc);
+    // (the copy engine moves a chunk at ~50 GB/s while the later chunks solve; stores of the kernels themselves into mapped host
+    //  memory sustain ~8.6 GB/s on MI355X -- measured, round 5 -- which a 4096-instance batch's 4 MB would just fit under, with
+    //  nothing to spare)
+    CHUNK_TRY(hipMemcpyAsync(h->pin_out.p + ck[c].out, dout, L.out_bytes, hipMemcpyDeviceToHost, st));
+    CHUNK_TRY(hipEventRecord(h->cev[c], st));
+  }
+  const double t_issued = timing ? now() : 0.0;
+  // ---- unpack chunk by chunk, as each arrives
+  for (int c = 0; c < plan.n; ++c) {
+    const PackedLayout& L = ck[c].L;
+    const size_t lo = plan.lo[c], nb = plan.nb[c];
+    const double tw0 = timing ? now() : 0.0;
+    CHUNK_TRY(hipEventSynchronize(h->cev[c]));
+    const double tw1 = timing ? now() : 0.0;
+    t_wait += tw1 - tw0; t_last_wait = tw1 - tw0;
+    if (timing) std::fprintf(stderr, "[bmpc host path]   chunk %d ready %.0f us after the call began (waited %.0f)\n", c, tw1 - t_begin, tw1 - tw0);
+    const char* src = h->pin_out.p + ck[c].out;
+    auto put = [&](T* dst, const float* from, size_t cnt) {
+      if constexpr (sizeof(T) == sizeof(float)) std::memcpy(dst, from, cnt * sizeof(float));
+      else for (size_t q = 0; q < cnt; ++q) dst[q] = (T)from[q];
+    };
+    put(controls + lo * H * 12, reinterpret_cast<const float*>(src + L.o_u), nb * H * 12);
+    if (states) put(states + lo * H * 13, reinterpret_cast<const float*>(src + L.o_s), nb * H * 13);
+    if (iters) std::memcpy(iters + lo, src + L.o_it, nb * 4);
+    if (status) std::memcpy(status + lo, src + L.o_st, nb * 4);
+    if (nfactor) std::memcpy(nfactor + lo, src + L.o_nf, nb * 4);
+    if (residuals) std::memcpy(residuals + lo * 2, src + L.o_rs, nb * 2 * 4);
+    if (timing) { const double tu = now() - tw1; t_unpack += tu; t_last_unpack = tu; }
+  }
+  if (timing)
+    std::fprintf(stderr, "[bmpc host path] B %d chunks %d: pack + issue %.0f us, waiting %.0f us (last chunk %.0f), unpack %.0f us (last chunk %.0f), total %.0f us\n",
+                 B, plan.n, t_issued - t_begin, t_wait, t_last_wait, t_unpack, t_last_unpack, now() - t_begin);
   return BMPC_OK;
 }
 
@@ -638,206 +837,25 @@ int bmpc_get_params(bmpc_handle h, bmpc_params* out) {
   return BMPC_OK;
 }
 
-// one solve launch with the dispatch order given explicitly (roll-outs use their own, the handle's stays untouched)
-// (ev: which of the handle's timing events this launch records -- bit 0: ev0 before it, bit 1: ev1 after it; a batch that goes
-//  out in chunks records ev0 before its first kernel and ev1 after its last, so bmpc_last_kernel_ms spans them all.
-//  c64 / s64: fp64 output arrays instead of controls / states, see bmpc::WarmArgs)
-static int solve_device_ordered(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
-                                const int32_t* phase, const float* x_cmd, const float* mu, float* controls,
-                                float* states, int32_t* iters, float* residuals, int32_t* status, int32_t* nfactor,
-                                void* stream, const int32_t* order, int ev = 3, double* c64 = nullptr, double* s64 = nullptr) {
-  int rc = check_common(h, B, x_fb, foot, contact, phase, c64 ? static_cast<const void*>(c64) : static_cast<const void*>(controls));
-  if (rc != BMPC_OK) return rc;
-  if (B == 0) return BMPC_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = pick_stream(h, stream);
-  bmpc::DebugOut dbg = {nullptr, nullptr, nullptr, nullptr, h->prof_dev, 0};
-  if (ev & 1) HIP_TRY(hipEventRecord(h->ev0, st));
-  rc = launch(h, B, x_fb, foot, contact, phase, x_cmd, mu, controls, states, iters, residuals, status, nfactor, dbg, st, order, c64, s64);
-  if (rc != BMPC_OK) return rc;
-  if (ev & 2) { HIP_TRY(hipEventRecord(h->ev1, st)); h->timed = true; }
-  return BMPC_OK;
-}
-
 int bmpc_solve_batch_device(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
                             const int32_t* phase, const float* x_cmd, const float* mu, float* controls,
                             float* states, int32_t* iters, float* residuals, int32_t* status, int32_t* nfactor,
                             void* stream) {
   if (!h) return fail(BMPC_ERR_INVALID, "null handle");
-  return solve_device_ordered(h, B, x_fb, foot, contact, phase, x_cmd, mu, controls, states, iters, residuals, status, nfactor,
-                              stream, h->order);
+  SolveIO io;
+  io.x_fb = x_fb; io.foot = foot; io.contact = contact; io.phase = phase; io.x_cmd = x_cmd; io.mu = mu;
+  io.controls = controls; io.states = states; io.iters = iters; io.resid = residuals; io.status = status; io.nfactor = nfactor;
+  return solve_device_ordered(h, B, io, stream, h->order);
 }
-
-// Host pointers in, host pointers out (T = float: bmpc_solve_batch; T = double: bmpc_solve_batch_f64, the dtype the reference
-// returns).  What the reference's callers get (REF:487), so PCIe is part of the path:
-//   * per chunk the inputs are packed into one pinned block and cross in ONE copy; outputs come back one packed block;
-//   * the batch is split into up to HOST_CHUNKS contiguous chunks, each launched on its own stream (descending priority:
-//     the dispatcher serves chunk 0's workgroups first), followed on that stream by the chunk's device-to-host copy: the
-//     results of chunk c cross PCIe, and are unpacked (widened to fp64) into the caller's pageable arrays by the calling thread,
-//     while chunks c + 1 .. still solve.  Only the last chunk's copy and unpacking are exposed.
-//     (A caller that can take its results in the handle's own page-locked block has no unpacking at all: bmpc_solve_batch_io.)
-// The kernels' arithmetic does not depend on the position in a batch, so the results are bit-identical to a single launch.
-// Warm start, a dispatch order and the profile buffer index by the instance's position in the whole batch: with any of them
-// set the batch goes out as one chunk.
-// Ordering: the chunk streams wait for what was queued on the handle's own stream before the call (a device-pointer solve on
-// BMPC_STREAM_OWN, its warm-start state), and the call returns with every chunk complete.
-}  // extern "C"  (a template cannot have C linkage)
-
-namespace {
-
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-template <typename T>
-int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact, const int32_t* phase,
-               const float* x_cmd, const float* mu, T* controls, T* states, int32_t* iters, float* residuals, int32_t* status,
-               int32_t* nfactor) {
-  int rc = check_common(h, B, x_fb, foot, contact, phase, controls);
-  if (rc != BMPC_OK) return rc;
-  if (B == 0) return BMPC_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B, H = (size_t)h->dev.h;
-  const bool timing = h->host_timing;                                 // (diagnostics: where a host-pointer call spends its time)
-  auto now = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_begin = timing ? now() : 0.0;
-  double t_wait = 0, t_unpack = 0, t_last_wait = 0, t_last_unpack = 0;
-  // ---- chunks: contiguous, one per stream priority the device offers (MI355X: three; chunks that share a priority are
-  // served round robin and finish together), the later ones smaller: the last chunk's unpacking is the exposed part,
-  // and a chunk's unpacking (~1/3 of its solve time) has to fit before the next chunk arrives.
-  const bool whole = h->warm_on || h->order || h->prof_dev;
-  int nchunk = whole ? 1 : (int)(n / 512);
-  nchunk = nchunk < 1 ? 1 : (nchunk > h->host_chunks ? h->host_chunks : nchunk);
-  const double* kCut4 = h->host_cut;
-  // per-instance bytes of a chunk's packed blocks.  in: x_fb, foot, phase [, x_cmd] [, mu], contact;
-  // out: controls [, states], iters, status, nfactor, residuals (every sub-array starts 16-byte aligned)
-  const size_t in_per = (12 + 6 + 1 + (x_cmd ? 12 : 0) + (mu ? 2 * H : 0)) * 4 + 2 * H;
-  const size_t out_per = (H * 12 + (states ? H * 13 : 0)) * 4 + 3 * 4 + 2 * 4;
-  const size_t in_bytes = n * in_per + (size_t)nchunk * 6 * 16, out_bytes = n * out_per + (size_t)nchunk * 6 * 16;
-  HIP_TRY(h->pin_in.ensure(in_bytes));
-  HIP_TRY(h->dev_in.ensure(in_bytes));
-  HIP_TRY(h->pin_out.ensure(out_bytes));
-  HIP_TRY(h->dev_out.ensure(out_bytes));
-  // what the handle's own stream holds (a device-pointer solve on BMPC_STREAM_OWN, the warm-start state it writes) comes first;
-  // an idle stream -- the usual case -- is not made to process a marker the chunk streams would then wait for (tens of us)
-  const bool own_busy = hipStreamQuery(h->stream) != hipSuccess;
-  if (own_busy) HIP_TRY(hipEventRecord(h->cev_own, h->stream));
-  struct Chunk { size_t lo, nb, off, o_u, o_s, o_it, o_st, o_nf, o_rs, bytes; } ck[bmpc_handle_s::HOST_CHUNKS];
-  size_t off = 0, ioff = 0;
-  int issued = 0;                               // chunks whose work is queued (an error below waits for them before returning)
-  auto bail = [&](int code) {
-    for (int c = 0; c < issued; ++c) (void)hipStreamSynchronize(h->cstream[c]);   // their copies still read pin_in / write pin_out
-    return code;
-  };
-#define HOST_TRY(expr)                                                                                   \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) return bail(fail(BMPC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)));       \
-  } while (0)
-  for (int c = 0; c < nchunk; ++c) {
-    Chunk& k = ck[c];
-    k.lo = nchunk >= 2 ? (size_t)(n * kCut4[c]) : 0;
-    k.nb = (nchunk >= 2 ? (size_t)(n * kCut4[c + 1]) : n) - k.lo;
-    if (c == nchunk - 1) k.nb = n - k.lo;
-    // inputs of this chunk: packed into the pinned block and sent in ONE copy (chunk 0 is on its way while the later
-    // chunks are still being packed)
-    const size_t i_xfb = 0, i_foot = align16(i_xfb + k.nb * 12 * 4), i_phase = align16(i_foot + k.nb * 6 * 4),
-                 i_xcmd = align16(i_phase + k.nb * 4), i_mu = align16(i_xcmd + (x_cmd ? k.nb * 12 * 4 : 0)),
-                 i_con = align16(i_mu + (mu ? k.nb * H * 2 * 4 : 0)), i_bytes = align16(i_con + k.nb * H * 2);
-    char* pin = h->pin_in.p + ioff;
-    char* din = h->dev_in.p + ioff;
-    ioff += i_bytes;
-    std::memcpy(pin + i_xfb, x_fb + k.lo * 12, k.nb * 12 * 4);
-    std::memcpy(pin + i_foot, foot + k.lo * 6, k.nb * 6 * 4);
-    std::memcpy(pin + i_phase, phase + k.lo, k.nb * 4);
-    if (x_cmd) std::memcpy(pin + i_xcmd, x_cmd + k.lo * 12, k.nb * 12 * 4);
-    if (mu) std::memcpy(pin + i_mu, mu + k.lo * H * 2, k.nb * H * 2 * 4);
-    std::memcpy(pin + i_con, contact + k.lo * H * 2, k.nb * H * 2);
-    k.off = off;
-    k.o_u = 0;
-    k.o_s = align16(k.o_u + k.nb * H * 12 * 4);
-    k.o_it = align16(k.o_s + (states ? k.nb * H * 13 * 4 : 0));
-    k.o_st = align16(k.o_it + k.nb * 4);
-    k.o_nf = align16(k.o_st + k.nb * 4);
-    k.o_rs = align16(k.o_nf + k.nb * 4);
-    k.bytes = align16(k.o_rs + k.nb * 2 * 4);
-    off += k.bytes;
-    hipStream_t st = h->cstream[c];
-    if (own_busy) HOST_TRY(hipStreamWaitEvent(st, h->cev_own, 0));
-    issued = c + 1;
-    HOST_TRY(hipMemcpyAsync(din, pin, i_bytes, hipMemcpyHostToDevice, st));
-    char* dout = h->dev_out.p + k.off;
-    rc = solve_device_ordered(h, (int)k.nb, reinterpret_cast<const float*>(din + i_xfb), reinterpret_cast<const float*>(din + i_foot),
-                              reinterpret_cast<const uint8_t*>(din + i_con), reinterpret_cast<const int32_t*>(din + i_phase),
-                              x_cmd ? reinterpret_cast<const float*>(din + i_xcmd) : nullptr,
-                              mu ? reinterpret_cast<const float*>(din + i_mu) : nullptr,
-                              reinterpret_cast<float*>(dout + k.o_u), states ? reinterpret_cast<float*>(dout + k.o_s) : nullptr,
-                              reinterpret_cast<int32_t*>(dout + k.o_it), reinterpret_cast<float*>(dout + k.o_rs),
-                              reinterpret_cast<int32_t*>(dout + k.o_st), reinterpret_cast<int32_t*>(dout + k.o_nf), st, h->order,
-                              (c == 0 ? 1 : 0) | (c == nchunk - 1 ? 2 : 0));
-    if (rc != BMPC_OK) return bail(rc);
-    // (the copy engine moves a chunk at ~50 GB/s while the later chunks solve; stores of the kernels themselves into mapped host
-    //  memory sustain ~8.6 GB/s on MI355X -- measured, round 5 -- which a 4096-instance batch's 4 MB would just fit under, with
-    //  nothing to spare)
-    HOST_TRY(hipMemcpyAsync(h->pin_out.p + k.off, dout, k.bytes, hipMemcpyDeviceToHost, st));
-    HOST_TRY(hipEventRecord(h->cev[c], st));
-  }
-  const double t_issued = timing ? now() : 0.0;
-  // ---- unpack chunk by chunk, as each arrives
-  for (int c = 0; c < nchunk; ++c) {
-    const Chunk& k = ck[c];
-    const double tw0 = timing ? now() : 0.0;
-    HOST_TRY(hipEventSynchronize(h->cev[c]));
-    const double tw1 = timing ? now() : 0.0;
-    t_wait += tw1 - tw0; t_last_wait = tw1 - tw0;
-    if (timing) std::fprintf(stderr, "[bmpc host path]   chunk %d ready %.0f us after the call began (waited %.0f)\n", c, tw1 - t_begin, tw1 - tw0);
-    const char* src = h->pin_out.p + k.off;
-    auto put = [&](T* dst, const float* from, size_t cnt) {
-      if constexpr (sizeof(T) == sizeof(float)) std::memcpy(dst, from, cnt * sizeof(float));
-      else for (size_t q = 0; q < cnt; ++q) dst[q] = (T)from[q];
-    };
-    put(controls + k.lo * H * 12, reinterpret_cast<const float*>(src + k.o_u), k.nb * H * 12);
-    if (states) put(states + k.lo * H * 13, reinterpret_cast<const float*>(src + k.o_s), k.nb * H * 13);
-    if (iters) std::memcpy(iters + k.lo, src + k.o_it, k.nb * 4);
-    if (status) std::memcpy(status + k.lo, src + k.o_st, k.nb * 4);
-    if (nfactor) std::memcpy(nfactor + k.lo, src + k.o_nf, k.nb * 4);
-    if (residuals) std::memcpy(residuals + k.lo * 2, src + k.o_rs, k.nb * 2 * 4);
-    if (timing) { const double tu = now() - tw1; t_unpack += tu; t_last_unpack = tu; }
-  }
-#undef HOST_TRY
-  if (timing)
-    std::fprintf(stderr, "[bmpc host path] B %d chunks %d: pack + issue %.0f us, waiting %.0f us (last chunk %.0f), unpack %.0f us (last chunk %.0f), total %.0f us\n",
-                 B, nchunk, t_issued - t_begin, t_wait, t_last_wait, t_unpack, t_last_unpack, now() - t_begin);
-  return BMPC_OK;
-}
-
-// layout of the handle's I/O block for a batch (bmpc_host_io): inputs | outputs, every array 64-byte aligned
-inline size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
-
-}  // namespace
-
-extern "C" {
 
 int bmpc_host_io(bmpc_handle h, int B, int with_x_cmd, int with_mu, int with_states, bmpc_host_views* out) {
   if (!h || !out) return fail(BMPC_ERR_INVALID, "null argument");
   if (B < 1 || B > h->max_batch) return fail(BMPC_ERR_INVALID, "batch %d outside [1, max_batch=%d]", B, h->max_batch);
   HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B, H = (size_t)h->dev.h;
   bmpc_handle_s::IoLayout& L = h->io;
-  L.B = 0;
+  // inputs | outputs, every array 64-byte aligned, fp64 controls and states; B = 0 (no layout) until the block is there
+  L = {packed_layout((size_t)B, (size_t)h->dev.h, with_x_cmd, with_mu, with_states, 64, 8)};
   h->io_gen = h->io_gen == 0x7fffffff ? 1 : h->io_gen + 1;
-  L.i_xfb = 0;
-  L.i_foot = align64(L.i_xfb + n * 12 * 4);
-  L.i_phase = align64(L.i_foot + n * 6 * 4);
-  L.i_xcmd = align64(L.i_phase + n * 4);
-  L.i_mu = align64(L.i_xcmd + (with_x_cmd ? n * 12 * 4 : 0));
-  L.i_con = align64(L.i_mu + (with_mu ? n * H * 2 * 4 : 0));
-  L.in_bytes = align64(L.i_con + n * H * 2);
-  L.o_u = 0;
-  L.o_s = align64(L.o_u + n * H * 12 * 8);
-  L.o_it = align64(L.o_s + (with_states ? n * H * 13 * 8 : 0));
-  L.o_st = align64(L.o_it + n * 4);
-  L.o_nf = align64(L.o_st + n * 4);
-  L.o_rs = align64(L.o_nf + n * 4);
-  L.out_bytes = align64(L.o_rs + n * 2 * 4);
   // (the handle's own stream may still read the old block: a re-allocation waits for it)
   if (L.in_bytes > h->io_in.n || L.out_bytes > h->io_out.n) HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(h->io_in.ensure(L.in_bytes));
@@ -879,52 +897,32 @@ int bmpc_solve_batch_io(bmpc_handle h, int B) {
   // controls (and the per-instance counters) go straight from the kernels' epilogues into the host arrays -- free below that
   // rate --, the states are stored in HBM and follow by copy engine, chunk by chunk on the chunk streams of the host-pointer
   // path, so that only the last chunk's copy (15 % of the states) is exposed.  Everything through the kernels: +0.12 ms.
-  const bool whole = h->warm_on || h->order || h->prof_dev || !L.states;     // (one chunk: everything straight from the kernel)
-  int nchunk = whole ? 1 : (int)(n / 512);
-  nchunk = nchunk < 1 ? 1 : (nchunk > h->host_chunks ? h->host_chunks : nchunk);
+  const ChunkPlan plan = plan_chunks(h, n, !L.states);     // (no states: one chunk, everything straight from the kernel)
   if (L.states) HIP_TRY(h->io_states.ensure(n * H * 13));
-  const bool own_busy = hipStreamQuery(h->stream) != hipSuccess;      // what the handle's own stream holds comes first
-  if (own_busy) HIP_TRY(hipEventRecord(h->cev_own, h->stream));
+  HIP_TRY(chunks_after_own_stream(h, plan.n));
   int issued = 0;
-  auto bail = [&](int code) {
-    for (int c = 0; c < issued; ++c) (void)hipStreamSynchronize(h->cstream[c]);
-    return code;
-  };
-#define IO_TRY(expr)                                                                                     \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) return bail(fail(BMPC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)));       \
-  } while (0)
-  for (int c = 0; c < nchunk; ++c) {
-    const size_t lo = nchunk >= 2 ? (size_t)(n * h->host_cut[c]) : 0;
-    const size_t nb = (c == nchunk - 1 ? n : (size_t)(n * h->host_cut[c + 1])) - lo;
+  for (int c = 0; c < plan.n; ++c) {
+    const size_t lo = plan.lo[c], nb = plan.nb[c];
     hipStream_t st = h->cstream[c];
-    if (own_busy) IO_TRY(hipStreamWaitEvent(st, h->cev_own, 0));
     issued = c + 1;
     if (c == 0) {                               // ONE copy in, for the whole batch
-      IO_TRY(hipMemcpyAsync(din, h->io_in.p, L.in_bytes, hipMemcpyHostToDevice, st));
-      IO_TRY(hipEventRecord(h->cev_in, st));
+      CHUNK_TRY(hipMemcpyAsync(din, h->io_in.p, L.in_bytes, hipMemcpyHostToDevice, st));
+      CHUNK_TRY(hipEventRecord(h->cev_in, st));
     } else {
-      IO_TRY(hipStreamWaitEvent(st, h->cev_in, 0));
+      CHUNK_TRY(hipStreamWaitEvent(st, h->cev_in, 0));
     }
     // (the last chunk's states go the way of the controls: nothing is left to copy when its kernel ends, and 15 % of the
     //  states on top of the controls stay well below what the kernels' own stores sustain)
-    const bool by_copy = L.states && c < nchunk - 1;
-    double* s64 = !L.states ? nullptr : (by_copy ? h->io_states.p + lo * H * 13 : reinterpret_cast<double*>(o + L.o_s) + lo * H * 13);
-    int rc = solve_device_ordered(h, (int)nb, reinterpret_cast<const float*>(din + L.i_xfb) + lo * 12, reinterpret_cast<const float*>(din + L.i_foot) + lo * 6,
-                                  reinterpret_cast<const uint8_t*>(din + L.i_con) + lo * H * 2, reinterpret_cast<const int32_t*>(din + L.i_phase) + lo,
-                                  L.x_cmd ? reinterpret_cast<const float*>(din + L.i_xcmd) + lo * 12 : nullptr,
-                                  L.mu ? reinterpret_cast<const float*>(din + L.i_mu) + lo * H * 2 : nullptr, nullptr, nullptr,
-                                  reinterpret_cast<int32_t*>(o + L.o_it) + lo, reinterpret_cast<float*>(o + L.o_rs) + lo * 2,
-                                  reinterpret_cast<int32_t*>(o + L.o_st) + lo, reinterpret_cast<int32_t*>(o + L.o_nf) + lo, st, h->order,
-                                  (c == 0 ? 1 : 0) | (c == nchunk - 1 ? 2 : 0),
-                                  reinterpret_cast<double*>(o + L.o_u) + lo * H * 12, s64);
-    if (rc != BMPC_OK) return bail(rc);
-    if (by_copy) IO_TRY(hipMemcpyAsync(reinterpret_cast<double*>(o + L.o_s) + lo * H * 13, s64, nb * H * 13 * sizeof(double), hipMemcpyDeviceToHost, st));
-    IO_TRY(hipEventRecord(h->cev[c], st));
+    const bool by_copy = L.states && c < plan.n - 1;
+    SolveIO io = packed_io(L, din, o, lo, H, L.x_cmd, L.mu);
+    io.controls64 = reinterpret_cast<double*>(o + L.o_u) + lo * H * 12;
+    if (L.states) io.states64 = by_copy ? h->io_states.p + lo * H * 13 : reinterpret_cast<double*>(o + L.o_s) + lo * H * 13;
+    if (int rc = solve_device_ordered(h, (int)nb, io, st, h->order, plan.events(c)); rc != BMPC_OK) return bail(h, issued, rc);
+    if (by_copy) CHUNK_TRY(hipMemcpyAsync(reinterpret_cast<double*>(o + L.o_s) + lo * H * 13, io.states64, nb * H * 13 * sizeof(double), hipMemcpyDeviceToHost, st));
+    CHUNK_TRY(hipEventRecord(h->cev[c], st));
   }
-  for (int c = 0; c < nchunk; ++c) IO_TRY(hipEventSynchronize(h->cev[c]));
-#undef IO_TRY
+  for (int c = 0; c < plan.n; ++c) CHUNK_TRY(hipEventSynchronize(h->cev[c]));
+#undef CHUNK_TRY
   return BMPC_OK;
 }
 
@@ -954,9 +952,7 @@ int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* fo
                         const int32_t* phase, const float* x_cmd, const float* mu, double* x_ref, double* foot_ref,
                         double* Gt, double* qt) {
   float dummy = 0;
-  int rc = check_common(h, B, x_fb, foot, contact, phase, &dummy);
-  if (rc != BMPC_OK) return rc;
-  if (B == 0) return BMPC_OK;
+  if (int rc = check_common(h, B, x_fb, foot, contact, phase, &dummy); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B, H = (size_t)h->dev.h, NW = 6 * H;
   HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->foot.ensure(n * 6)); HIP_TRY(h->contact.ensure(n * H * 2));
@@ -979,9 +975,11 @@ int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* fo
   if (x_cmd) HIP_TRY(hipMemcpyAsync(h->x_cmd.p, x_cmd, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
   if (mu) HIP_TRY(hipMemcpyAsync(h->mu.p, mu, n * H * 2 * sizeof(float), hipMemcpyHostToDevice, st));
   bmpc::DebugOut dbg = {h->dbg.p + o_xr, h->dbg.p + o_fr, Gt ? h->dbg.p + o_gt : nullptr, qt ? h->dbg.p + o_qt : nullptr, nullptr, 1};
-  rc = launch(h, B, h->x_fb.p, h->foot.p, h->contact.p, h->phase.p, x_cmd ? h->x_cmd.p : nullptr,
-              mu ? h->mu.p : nullptr, h->controls.p, nullptr, nullptr, nullptr, nullptr, nullptr, dbg, st, nullptr);
-  if (rc != BMPC_OK) return rc;
+  SolveIO io;
+  io.x_fb = h->x_fb.p; io.foot = h->foot.p; io.contact = h->contact.p; io.phase = h->phase.p; io.controls = h->controls.p;
+  if (x_cmd) io.x_cmd = h->x_cmd.p;
+  if (mu) io.mu = h->mu.p;
+  if (int rc = launch(h, B, io, dbg, st, nullptr); rc != BMPC_OK) return rc;
   if (x_ref) HIP_TRY(hipMemcpyAsync(x_ref, h->dbg.p + o_xr, n * H * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
   if (foot_ref) HIP_TRY(hipMemcpyAsync(foot_ref, h->dbg.p + o_fr, n * H * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
   if (Gt) HIP_TRY(hipMemcpyAsync(Gt, h->dbg.p + o_gt, n * NW * NW * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1000,9 +998,7 @@ static bmpc::LowLevelParams ll_params(const bmpc_params& p) {
 }
 
 int bmpc_foot_position_world_device(bmpc_handle h, int B, const float* x_fb, const float* q, float* pf_w, void* stream) {
-  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
-  if (B < 0 || B > h->max_batch) return fail(BMPC_ERR_INVALID, "batch %d outside [0, max_batch=%d]", B, h->max_batch);
-  if (B == 0) return BMPC_OK;
+  if (int rc = check_batch(h, B); rc <= 0) return rc;
   if (!x_fb || !q || !pf_w) return fail(BMPC_ERR_INVALID, "null pointer");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = pick_stream(h, stream);
@@ -1012,9 +1008,7 @@ int bmpc_foot_position_world_device(bmpc_handle h, int B, const float* x_fb, con
 }
 
 int bmpc_foot_position_world(bmpc_handle h, int B, const float* x_fb, const float* q, float* pf_w) {
-  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
-  if (B < 0 || B > h->max_batch) return fail(BMPC_ERR_INVALID, "batch %d outside [0, max_batch=%d]", B, h->max_batch);
-  if (B == 0) return BMPC_OK;
+  if (int rc = check_batch(h, B); rc <= 0) return rc;
   if (!x_fb || !q || !pf_w) return fail(BMPC_ERR_INVALID, "null pointer");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B;
@@ -1032,9 +1026,7 @@ int bmpc_foot_position_world(bmpc_handle h, int B, const float* x_fb, const floa
 int bmpc_low_level_control_device(bmpc_handle h, int B, const float* x_fb, const double* t, const float* pf_w,
                                   const float* q, const float* qd, const uint8_t* contact0, const float* u0,
                                   float* tau, void* stream) {
-  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
-  if (B < 0 || B > h->max_batch) return fail(BMPC_ERR_INVALID, "batch %d outside [0, max_batch=%d]", B, h->max_batch);
-  if (B == 0) return BMPC_OK;
+  if (int rc = check_batch(h, B); rc <= 0) return rc;
   if (!x_fb || !t || !pf_w || !q || !qd || !contact0 || !u0 || !tau) return fail(BMPC_ERR_INVALID, "null pointer");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = pick_stream(h, stream);
@@ -1046,9 +1038,7 @@ int bmpc_low_level_control_device(bmpc_handle h, int B, const float* x_fb, const
 
 int bmpc_low_level_control(bmpc_handle h, int B, const float* x_fb, const double* t, const float* pf_w,
                            const float* q, const float* qd, const uint8_t* contact0, const float* u0, float* tau) {
-  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
-  if (B < 0 || B > h->max_batch) return fail(BMPC_ERR_INVALID, "batch %d outside [0, max_batch=%d]", B, h->max_batch);
-  if (B == 0) return BMPC_OK;
+  if (int rc = check_batch(h, B); rc <= 0) return rc;
   if (!x_fb || !t || !pf_w || !q || !qd || !contact0 || !u0 || !tau) return fail(BMPC_ERR_INVALID, "null pointer");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B;
@@ -1094,9 +1084,7 @@ static int gait_params(bmpc_handle h, const bmpc_gait* gait, bmpc::GaitParams* G
 
 int bmpc_contact_sequence_device(bmpc_handle h, int B, const double* t, const bmpc_gait* gait, int32_t* phase,
                                  uint8_t* contact, void* stream) {
-  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
-  if (B < 0 || B > h->max_batch) return fail(BMPC_ERR_INVALID, "batch %d outside [0, max_batch=%d]", B, h->max_batch);
-  if (B == 0) return BMPC_OK;
+  if (int rc = check_batch(h, B); rc <= 0) return rc;
   if (!t) return fail(BMPC_ERR_INVALID, "null pointer");
   bmpc::GaitParams G;
   int rc = gait_params(h, gait, &G);
@@ -1109,9 +1097,7 @@ int bmpc_contact_sequence_device(bmpc_handle h, int B, const double* t, const bm
 }
 
 int bmpc_contact_sequence(bmpc_handle h, int B, const double* t, const bmpc_gait* gait, int32_t* phase, uint8_t* contact) {
-  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
-  if (B < 0 || B > h->max_batch) return fail(BMPC_ERR_INVALID, "batch %d outside [0, max_batch=%d]", B, h->max_batch);
-  if (B == 0) return BMPC_OK;
+  if (int rc = check_batch(h, B); rc <= 0) return rc;
   if (!t) return fail(BMPC_ERR_INVALID, "null pointer");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B, hh = (size_t)h->params.h;
@@ -1146,8 +1132,7 @@ int bmpc_reset_warm_start(bmpc_handle h) {
 int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const float* foot, double* t,
                         const bmpc_gait* gait, const float* x_cmd, const float* mu, float* u0_traj, float* x_traj,
                         int32_t* iters_traj, int32_t* status_any, void* stream) {
-  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
-  if (B < 0 || B > h->max_batch) return fail(BMPC_ERR_INVALID, "batch %d outside [0, max_batch=%d]", B, h->max_batch);
+  if (int rc = check_batch(h, B); rc < 0) return rc;
   if (steps < 0) return fail(BMPC_ERR_INVALID, "steps must be >= 0");
   if (B == 0 || steps == 0) return BMPC_OK;
   if (!x_fb || !foot || !t) return fail(BMPC_ERR_INVALID, "x_fb, foot and t must be non-null");
@@ -1161,6 +1146,9 @@ int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const floa
   const int32_t* order = h->order;                 // this roll-out's dispatch order (the handle's is left alone)
   const bool own_order = h->longest_first && !order;
   if (own_order) HIP_TRY(h->ro_order.ensure(n));
+  SolveIO io;
+  io.x_fb = x_fb; io.foot = foot; io.contact = h->ro_contact.p; io.phase = h->ro_phase.p; io.x_cmd = x_cmd; io.mu = mu;
+  io.controls = h->ro_controls.p; io.states = h->ro_states.p; io.iters = h->ro_iters.p; io.status = h->ro_status.p;
   int rc = BMPC_OK;
   for (int s = 0; s < steps && rc == BMPC_OK; ++s) {
     // t -> (phase, contact) -> solve -> x_fb <- states[:, 0], t += dt: three launches on one stream, no host arithmetic
@@ -1172,8 +1160,7 @@ int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const floa
       if (hipGetLastError() != hipSuccess) { rc = fail(BMPC_ERR_HIP, "dispatch-order launch failed"); break; }
       order = h->ro_order.p;
     }
-    rc = solve_device_ordered(h, B, x_fb, foot, h->ro_contact.p, h->ro_phase.p, x_cmd, mu, h->ro_controls.p,
-                              h->ro_states.p, h->ro_iters.p, nullptr, h->ro_status.p, nullptr, stream, order);
+    rc = solve_device_ordered(h, B, io, stream, order);
     if (rc != BMPC_OK) break;
     hipLaunchKernelGGL(bmpc::rollout_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, (int)H, h->params.dt,
                        h->ro_states.p, h->ro_controls.p, h->ro_iters.p, h->ro_status.p, x_fb, t,

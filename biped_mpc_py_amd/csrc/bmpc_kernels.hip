@@ -2105,6 +2105,7 @@ solve_body(const DevParams& P, const int B,
   }
 }
 
+// (the stage-structured kernels of bmpc_stage.hip take the same list; it is undefined at the end of that file)
 #define BMPC_SOLVE_ARGS                                                                                            \
   const DevParams P, const int B, const float* __restrict__ x_fb, const float* __restrict__ foot,                  \
       const uint8_t* __restrict__ contact, const int32_t* __restrict__ phase, const float* __restrict__ x_cmd,     \
@@ -2121,6 +2122,5 @@ __global__ void __launch_bounds__(Dims<H>::NT, Dims<H>::WPE) solve_kernel_prof(B
   solve_body<H, true>(P, B, x_fb, foot, contact, phase, x_cmd, mu_in, controls, states, iters_out, resid_out, status_out,
                       nfactor_out, dbg, warm);
 }
-#undef BMPC_SOLVE_ARGS
 
 }  // namespace bmpc

@@ -1735,19 +1735,14 @@ stage_body(const DevParams& P, const int B,
 #undef BMPC_STEP
 }
 
-#define BMPC_STAGE_ARGS                                                                                            \
-  const DevParams P, const int B, const float* __restrict__ x_fb, const float* __restrict__ foot,                  \
-      const uint8_t* __restrict__ contact, const int32_t* __restrict__ phase, const float* __restrict__ x_cmd,     \
-      const float* __restrict__ mu_in, float* __restrict__ controls, float* __restrict__ states,                   \
-      int32_t* __restrict__ iters_out, float* __restrict__ resid_out, int32_t* __restrict__ status_out,            \
-      int32_t* __restrict__ nfactor_out, const DebugOut dbg, const WarmArgs warm
+// (the dense kernels' parameter list, bmpc_kernels.hip)
 template <int NP, int NW>
-__global__ void __launch_bounds__(64 * NW) stage_kernel(BMPC_STAGE_ARGS) {
+__global__ void __launch_bounds__(64 * NW) stage_kernel(BMPC_SOLVE_ARGS) {
   stage_body<NP, NW, false>(P, B, x_fb, foot, contact, phase, x_cmd, mu_in, controls, states, iters_out, resid_out, status_out,
                             nfactor_out, dbg, warm);
 }
 template <int NP, int NW>
-__global__ void __launch_bounds__(64 * NW) stage_kernel_prof(BMPC_STAGE_ARGS) {
+__global__ void __launch_bounds__(64 * NW) stage_kernel_prof(BMPC_SOLVE_ARGS) {
   stage_body<NP, NW, true>(P, B, x_fb, foot, contact, phase, x_cmd, mu_in, controls, states, iters_out, resid_out, status_out,
                            nfactor_out, dbg, warm);
 }
@@ -1757,6 +1752,6 @@ __host__ __device__ constexpr int stage_steps_per_lane(int h) {
   const int np = (h + 5 * stage_waves(h) - 1) / (5 * stage_waves(h));
   return np < 2 ? 2 : np;                      // (h <= 5: the smallest variant, most of its lane map phantoms)
 }
-#undef BMPC_STAGE_ARGS
+#undef BMPC_SOLVE_ARGS
 
 }  // namespace bmpc

@@ -264,8 +264,10 @@ typedef struct bmpc_host_views {
 } bmpc_host_views;
 int bmpc_host_io(bmpc_handle h, int B, int with_x_cmd, int with_mu, int with_states, bmpc_host_views* out);
 int bmpc_solve_batch_io(bmpc_handle h, int B);
-/* Layout generation of the handle's I/O block (ABI 11): a counter that moves with EVERY bmpc_host_io call of the handle, failed
- * ones included (a failed call leaves no layout: bmpc_solve_batch_io then refuses).  A caller that caches the views compares it
+/* Layout generation of the handle's I/O block (ABI 11): a counter that moves with every bmpc_host_io call of the handle that gets
+ * past argument validation.  A call rejected there (null handle or views, B out of range, hipSetDevice failing) leaves both the
+ * layout and the counter as they were; a call that fails after that point still moves the counter and leaves no layout
+ * (bmpc_solve_batch_io then refuses).  A caller that caches the views compares it
  * with the value it read after its own bmpc_host_io: any other layout call in between -- same B, other with_* flags, hence other
  * offsets -- shows, instead of the cached views being trusted.  Returns the counter (>= 0), or a negative error code. */
 int bmpc_host_io_generation(bmpc_handle h);
