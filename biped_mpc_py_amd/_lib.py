@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbmpc.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 # every symbol include/bmpc.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = (
@@ -19,6 +19,7 @@ EXPORTS = (
     "bmpc_solve_batch", "bmpc_solve_batch_f64", "bmpc_solve_batch_device", "bmpc_synchronize",
     "bmpc_host_io", "bmpc_solve_batch_io", "bmpc_host_io_generation",
     "bmpc_debug_assemble", "bmpc_debug_set_profile", "bmpc_last_kernel_ms",
+    "bmpc_solve_inputs_f64", "bmpc_solve_inputs_device", "bmpc_debug_assemble_inputs",
     "bmpc_foot_position_world", "bmpc_foot_position_world_device",
     "bmpc_low_level_control", "bmpc_low_level_control_device",
     "bmpc_gait_default", "bmpc_contact_sequence", "bmpc_contact_sequence_device",
@@ -35,6 +36,11 @@ class CHostViews(C.Structure):
     """`bmpc_host_views` of include/bmpc.h: the arrays of a handle's page-locked I/O block."""
     _fields_ = [(n, C.c_void_p) for n in ("x_fb", "foot", "contact", "phase", "x_cmd", "mu", "controls", "states",
                                            "iters", "residuals", "status", "nfactor")]
+
+
+class CInputs(C.Structure):
+    """`bmpc_inputs` of include/bmpc.h: the inputs of a solve, supplied references included (NULL: generated)."""
+    _fields_ = [(n, C.c_void_p) for n in ("x_fb", "foot", "contact", "phase", "x_cmd", "mu", "x_ref", "foot_ref")]
 
 
 class BmpcError(RuntimeError):
@@ -123,6 +129,9 @@ def load():
     lib.bmpc_host_io_generation.argtypes = [vp]
     lib.bmpc_debug_assemble.argtypes = [vp, ip] + [vp] * 10
     lib.bmpc_debug_set_profile.argtypes = [vp, vp]
+    lib.bmpc_solve_inputs_f64.argtypes = [vp, ip, C.POINTER(CInputs)] + [vp] * 6
+    lib.bmpc_solve_inputs_device.argtypes = [vp, ip, C.POINTER(CInputs)] + [vp] * 6 + [vp]
+    lib.bmpc_debug_assemble_inputs.argtypes = [vp, ip, C.POINTER(CInputs)] + [vp] * 4
     lib.bmpc_foot_position_world.argtypes = [vp, ip, vp, vp, vp]
     lib.bmpc_foot_position_world_device.argtypes = [vp, ip, vp, vp, vp, vp]
     lib.bmpc_low_level_control.argtypes = [vp, ip] + [vp] * 8

@@ -66,6 +66,51 @@ def get_contact_sequence(t, mpc, half=None):
     return np.stack([leg0, ~leg0], axis=1).astype(int)
 
 
+def _kernel_refs(x_ref, foot_ref, B, h):
+    """Supplied references in the kernel layout -- x_ref (B,h,12), foot_ref (B,h,6), each or None -- as C-contiguous fp32 arrays
+    (what `bmpc_inputs` takes).  Raises ValueError on a wrong shape or a non-finite value: a bad reference is the caller's
+    mistake, caught before the call (on the device it would only show as status 2 of that instance)."""
+    out = []
+    for name, a, w in (("x_ref", x_ref, 12), ("foot_ref", foot_ref, 6)):
+        if a is None:
+            out.append(None)
+            continue
+        a = np.asarray(a)
+        if a.shape != (B, h, w):
+            raise ValueError(f"{name} must have shape ({B}, {h}, {w}) (kernel layout: row j = step j), got {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{name} holds non-finite values")
+        out.append(np.ascontiguousarray(a, np.float32))
+    return out[0], out[1]
+
+
+def references_to_kernel_layout(x_ref=None, foot_ref=None, h=None):
+    """The reference's orientation -> the kernel layout, exactly (a transpose): x_ref (...,13,h) or (...,12,h) as
+    `get_reference_trajectory` / `reference_trajectories_batch` return it -> (...,h,12); foot_ref (...,6,h) -> (...,h,6).
+    A 13th row must be all ones (REF:62): anything else would silently change what Q[12] weighs, so it raises ValueError, as do
+    a wrong shape and non-finite values.  Values stay fp64 here; the solve takes them in fp32."""
+    xr = fr = None
+    if x_ref is not None:
+        a = np.asarray(x_ref, np.float64)
+        if a.ndim < 2 or a.shape[-2] not in (12, 13) or (h is not None and a.shape[-1] != h):
+            raise ValueError(f"x_ref must have shape (..., 13, h) or (..., 12, h){'' if h is None else f' with h = {h}'}, got {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError("x_ref holds non-finite values")
+        if a.shape[-2] == 13:
+            if not np.all(a[..., 12, :] == 1.0):
+                raise ValueError("row 12 of x_ref (the row of ones, REF:62) must be all ones")
+            a = a[..., :12, :]
+        xr = np.ascontiguousarray(np.swapaxes(a, -1, -2))
+    if foot_ref is not None:
+        a = np.asarray(foot_ref, np.float64)
+        if a.ndim < 2 or a.shape[-2] != 6 or (h is not None and a.shape[-1] != h):
+            raise ValueError(f"foot_ref must have shape (..., 6, h){'' if h is None else f' with h = {h}'}, got {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError("foot_ref holds non-finite values")
+        fr = np.ascontiguousarray(np.swapaxes(a, -1, -2))
+    return xr, fr
+
+
 def _ptr(a):
     """Address of a NumPy array as an integer (what a `c_void_p` parameter takes; building a ctypes pointer object per argument
     costs ~2 us each, fourteen of them per solve)."""
@@ -129,7 +174,7 @@ class BatchSolver:
         h = self.h
         x_fb = np.ascontiguousarray(np.asarray(x_fb, np.float32).reshape(-1, 12))
         B = x_fb.shape[0]
-        foot = np.ascontiguousarray(np.asarray(foot, np.float32).reshape(B, 6))
+        foot = None if foot is None else np.ascontiguousarray(np.asarray(foot, np.float32).reshape(B, 6))
         contact = _contact_u8(contact, B, h)
         phase = np.ascontiguousarray(np.asarray(phase, np.int32).reshape(B))
         if x_cmd is not None:
@@ -138,12 +183,17 @@ class BatchSolver:
             mu = np.ascontiguousarray(np.asarray(mu, np.float32).reshape(B, h, 2))
         return B, x_fb, foot, contact, phase, x_cmd, mu
 
-    def solve(self, x_fb, foot, contact, phase, x_cmd=None, mu=None, want_states=True, out=None):
+    def solve(self, x_fb, foot, contact, phase, x_cmd=None, mu=None, want_states=True, out=None, x_ref=None, foot_ref=None):
         """Host arrays in, host arrays out (fp32 over PCIe, fp64 returned -- the reference's dtype, REF:300-304; the
         widening happens inside `bmpc_solve_batch_f64` while the results are unpacked, overlapped with the solve).  Returns
         (states (B,h,13) | None, controls (B,h,12), info).  `out`: optional (states | None, controls) fp64 C-contiguous
-        arrays of those shapes to write into (a control loop reuses its buffers instead of allocating 8 MB per call)."""
+        arrays of those shapes to write into (a control loop reuses its buffers instead of allocating 8 MB per call).
+        `x_ref` (B,h,12) / `foot_ref` (B,h,6): references to track instead of the generated ones (`bmpc_solve_inputs_f64`,
+        include/bmpc.h; kernel layout, row j = step j); `foot` may then be None if `foot_ref` is given."""
         B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
+        x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h)
+        if foot is None and foot_ref is None:
+            raise ValueError("foot is required unless foot_ref is given")
         h = self.h
         if out is not None:
             states, controls = out
@@ -161,9 +211,14 @@ class BatchSolver:
         status = np.empty(B, np.int32)
         nfactor = np.empty(B, np.int32)
         resid = np.empty((B, 2), np.float32)
-        _lib.check(self._lib.bmpc_solve_batch_f64(
-            self._h, B, _ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu),
-            _ptr(controls), _ptr(states), _ptr(iters), _ptr(resid), _ptr(status), _ptr(nfactor)))
+        if x_ref is None and foot_ref is None:
+            _lib.check(self._lib.bmpc_solve_batch_f64(
+                self._h, B, _ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu),
+                _ptr(controls), _ptr(states), _ptr(iters), _ptr(resid), _ptr(status), _ptr(nfactor)))
+        else:
+            inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
+            _lib.check(self._lib.bmpc_solve_inputs_f64(
+                self._h, B, C.byref(inp), _ptr(controls), _ptr(states), _ptr(iters), _ptr(resid), _ptr(status), _ptr(nfactor)))
         info = dict(iters=iters, status=status, nfactor=nfactor, residuals=resid)
         return states, controls, info
 
@@ -233,28 +288,38 @@ class BatchSolver:
         info = dict(iters=io["iters"], status=io["status"], nfactor=io["nfactor"], residuals=io["residuals"])
         return io["states"], io["controls"], info
 
-    def assemble(self, x_fb, foot, contact, phase, x_cmd=None, mu=None, want_matrices=True):
+    def assemble(self, x_fb, foot, contact, phase, x_cmd=None, mu=None, want_matrices=True, x_ref=None, foot_ref=None):
         """Assembly stage only (parity tests, reference generators): x_ref (B,h,12), foot_ref (B,h,6) and -- with
         `want_matrices`, dense family only (h <= 20) -- Gt (B,6h,6h), qt (B,6h), else None for both.  Without them the
-        launch runs on the handle's own kernel family at every supported horizon and nothing of size (6h)^2 is allocated."""
+        launch runs on the handle's own kernel family at every supported horizon and nothing of size (6h)^2 is allocated.
+        Supplied `x_ref` / `foot_ref` (kernel layout, as `solve`) are what the assembly is built from and come back widened."""
         B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
+        xr_in, fr_in = _kernel_refs(x_ref, foot_ref, B, self.h)
+        if foot is None and fr_in is None:
+            raise ValueError("foot is required unless foot_ref is given")
         h = self.h
         x_ref = np.zeros((B, h, 12)); foot_ref = np.zeros((B, h, 6))
         Gt = np.zeros((B, 6 * h, 6 * h)) if want_matrices else None
         qt = np.zeros((B, 6 * h)) if want_matrices else None
-        _lib.check(self._lib.bmpc_debug_assemble(
-            self._h, B, _ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu),
-            _ptr(x_ref), _ptr(foot_ref), _ptr(Gt), _ptr(qt)))
+        if xr_in is None and fr_in is None:
+            _lib.check(self._lib.bmpc_debug_assemble(
+                self._h, B, _ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu),
+                _ptr(x_ref), _ptr(foot_ref), _ptr(Gt), _ptr(qt)))
+        else:
+            inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(xr_in), _ptr(fr_in))
+            _lib.check(self._lib.bmpc_debug_assemble_inputs(self._h, B, C.byref(inp), _ptr(x_ref), _ptr(foot_ref), _ptr(Gt), _ptr(qt)))
         return x_ref, foot_ref, Gt, qt
 
     # ---- device-resident (torch tensors are only a way to own HBM and a stream) ----------------
     def solve_device(self, x_fb, foot, contact, phase, x_cmd=None, mu=None, controls=None, states=None,
-                     iters=None, residuals=None, status=None, nfactor=None, stream=None):
+                     iters=None, residuals=None, status=None, nfactor=None, stream=None, x_ref=None, foot_ref=None):
         """Inputs/outputs are CUDA(HIP) torch tensors on this solver's device (fp32 / uint8 / int32,
         contiguous).  Asynchronous on `stream` (default: torch's current stream).  Returns the
         output tensors; nothing crosses PCIe.  `stream` is a raw hipStream_t value; torch's default stream
         is HIP's null stream (value 0) and is passed on as such, so the launch is ordered against the
-        surrounding torch work like any torch kernel."""
+        surrounding torch work like any torch kernel.  `x_ref` (B,h,12) / `foot_ref` (B,h,6) float32 tensors: references to track
+        (`bmpc_solve_inputs_device`); `foot` may then be None if `foot_ref` is given.  Their values are not checked here (that
+        would synchronise): a non-finite one shows as status 2 of its instance."""
         import torch
         B = x_fb.shape[0]
         h = self.h
@@ -272,6 +337,16 @@ class BatchSolver:
         if controls is None:
             controls = torch.empty((B, h, 12), dtype=torch.float32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        if x_ref is not None or foot_ref is not None:
+            inp = _lib.CInputs(chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)) or None,
+                               chk(contact, torch.uint8, (B, h, 2)), chk(phase, torch.int32, (B,)),
+                               chk(x_cmd, torch.float32, (B, 12)) or None, chk(mu, torch.float32, (B, h, 2)) or None,
+                               chk(x_ref, torch.float32, (B, h, 12)) or None, chk(foot_ref, torch.float32, (B, h, 6)) or None)
+            _lib.check(self._lib.bmpc_solve_inputs_device(
+                self._h, B, C.byref(inp), chk(controls, torch.float32, (B, h, 12)), chk(states, torch.float32, (B, h, 13)) or None,
+                chk(iters, torch.int32, (B,)) or None, chk(residuals, torch.float32, (B, 2)) or None,
+                chk(status, torch.int32, (B,)) or None, chk(nfactor, torch.int32, (B,)) or None, st))
+            return controls, states
         _lib.check(self._lib.bmpc_solve_batch_device(
             self._h, B, chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)),
             chk(contact, torch.uint8, (B, h, 2)), chk(phase, torch.int32, (B,)),
@@ -462,26 +537,30 @@ def close_cached_solvers():
 
 
 def solve_mpc_batch(x_fb, t, foot, contact, mpc=None, biped=None, x_cmd=None, mu=None, phase=None, half=None,
-                    device=0, solver_options=None, return_info=False):
+                    device=0, solver_options=None, return_info=False, x_ref=None, foot_ref=None):
     """B instances of REF:187 `solve_mpc`.  x_fb (B,12), t (B,) seconds [or phase (B,) directly],
     foot (B,6), contact (B,h,2); optional per-instance x_cmd (B,12) and mu (B,h,2).
+    Optional references to track instead of the generated ones, in the reference's orientation: x_ref (B,13,h) (or (B,12,h)) and
+    foot_ref (B,6,h) -- what `reference_trajectories_batch` returns, so "generate, edit, pass back" works.
     Returns states (B,h,13), controls (B,h,12) [, info].  Without `return_info` a NaN/Inf instance raises
     FloatingPointError and instances stopped at the iteration cap raise a SolverStatusWarning."""
     from .params import MPC
     mpc = mpc if mpc is not None else MPC()
+    xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
     solver = _cached_solver(mpc, biped, half, device, solver_options)
     if phase is None:
         phase = phase_indices(t, mpc.dt, mpc.h)
-    states, controls, info = solver.solve(x_fb, foot, contact, phase, x_cmd=x_cmd, mu=mu)
+    states, controls, info = solver.solve(x_fb, foot, contact, phase, x_cmd=x_cmd, mu=mu, x_ref=xr, foot_ref=fr)
     if return_info:
         return states, controls, info
     _check_status(info, "solve_mpc")
     return states, controls
 
 
-def solve_mpc(x_fb, t, foot, mpc, biped, contact, half=None, device=0, solver_options=None):
+def solve_mpc(x_fb, t, foot, mpc, biped, contact, half=None, device=0, solver_options=None, x_ref=None, foot_ref=None):
     """Drop-in for REF:187-304: same arguments, same return shapes and dtypes (fp64 `states (h,13)`,
-    `controls (h,12)`), inputs not mutated, silent."""
+    `controls (h,12)`), inputs not mutated, silent.  `x_ref` (13,h) / `foot_ref` (6,h): what the solve tracks in place of
+    REF:61-70 / REF:72-109 -- e.g. `get_reference_trajectory(...)` edited (stairs, a crouch, a planner's footholds)."""
     h = int(mpc.h)
     contact = np.asarray(contact)
     if contact.ndim != 2 or contact.shape[1] != 2 or contact.shape[0] < h:
@@ -489,7 +568,9 @@ def solve_mpc(x_fb, t, foot, mpc, biped, contact, half=None, device=0, solver_op
     x_fb = np.asarray(x_fb, float).reshape(12)
     foot = np.asarray(foot, float).reshape(6)
     states, controls = solve_mpc_batch(x_fb[None], [t], foot[None], contact[None, :h, :], mpc=mpc, biped=biped,
-                                       half=half, device=device, solver_options=solver_options)
+                                       half=half, device=device, solver_options=solver_options,
+                                       x_ref=None if x_ref is None else np.asarray(x_ref)[None],
+                                       foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None])
     return states[0], controls[0]
 
 

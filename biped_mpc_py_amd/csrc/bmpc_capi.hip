@@ -259,13 +259,15 @@ struct DevBuf {
 };
 
 // Offsets of the packed arrays of n instances, every array `align`-byte aligned (a power of two).  Inputs: x_fb, foot, phase
-// [, x_cmd] [, mu], contact; outputs: controls [, states] in elements of out_elem bytes (f32 or f64), iters, status, nfactor,
+// [, x_cmd] [, mu], contact [, x_ref] [, foot_ref] (the last two after everything else: without them the layout is the one the
+// handle's I/O block has always had); outputs: controls [, states] in elements of out_elem bytes (f32 or f64), iters, status, nfactor,
 // residuals.
 struct PackedLayout {
-  size_t i_xfb = 0, i_foot = 0, i_phase = 0, i_xcmd = 0, i_mu = 0, i_con = 0, in_bytes = 0;
+  size_t i_xfb = 0, i_foot = 0, i_phase = 0, i_xcmd = 0, i_mu = 0, i_con = 0, i_xref = 0, i_fref = 0, in_bytes = 0;
   size_t o_u = 0, o_s = 0, o_it = 0, o_st = 0, o_nf = 0, o_rs = 0, out_bytes = 0;
 };
-PackedLayout packed_layout(size_t n, size_t H, bool x_cmd, bool mu, bool states, size_t align, size_t out_elem) {
+PackedLayout packed_layout(size_t n, size_t H, bool x_cmd, bool mu, bool states, size_t align, size_t out_elem,
+                           bool x_ref = false, bool foot_ref = false) {
   auto up = [align](size_t v) { return (v + align - 1) & ~(align - 1); };
   PackedLayout L;
   L.i_foot = up(L.i_xfb + n * 12 * 4);
@@ -273,7 +275,9 @@ PackedLayout packed_layout(size_t n, size_t H, bool x_cmd, bool mu, bool states,
   L.i_xcmd = up(L.i_phase + n * 4);
   L.i_mu = up(L.i_xcmd + (x_cmd ? n * 12 * 4 : 0));
   L.i_con = up(L.i_mu + (mu ? n * H * 2 * 4 : 0));
-  L.in_bytes = up(L.i_con + n * H * 2);
+  L.i_xref = up(L.i_con + n * H * 2);
+  L.i_fref = up(L.i_xref + (x_ref ? n * H * 12 * 4 : 0));
+  L.in_bytes = up(L.i_fref + (foot_ref ? n * H * 6 * 4 : 0));
   L.o_s = up(L.o_u + n * H * 12 * out_elem);
   L.o_it = up(L.o_s + (states ? n * H * 13 * out_elem : 0));
   L.o_st = up(L.o_it + n * 4);
@@ -321,6 +325,7 @@ struct bmpc_handle_s {
     bool x_cmd = false, mu = false, states = false;
   } io;
   DevBuf<float> x_fb, foot, x_cmd, mu, controls, states, resid;
+  DevBuf<float> x_ref, foot_ref;    // supplied references of bmpc_debug_assemble_inputs
   DevBuf<uint8_t> contact;
   DevBuf<int32_t> phase, iters, status, nfactor;
   DevBuf<double> dbg;
@@ -359,6 +364,8 @@ struct SolveIO {
   const int32_t* phase = nullptr;
   const float* x_cmd = nullptr;
   const float* mu = nullptr;
+  const float* x_ref = nullptr;      // supplied references or null (bmpc_inputs; bmpc::WarmArgs)
+  const float* foot_ref = nullptr;
   float* controls = nullptr;
   float* states = nullptr;
   int32_t* iters = nullptr;
@@ -374,7 +381,9 @@ struct SolveIO {
 template <typename Kernel>
 int launch_family(bmpc_handle hd, int B, size_t warm_per_inst, const SolveIO& io, const bmpc::DebugOut& dbg,
                   const int32_t* order, const int32_t* rescue_status, Kernel kernel) {
-  bmpc::WarmArgs warm = {nullptr, 0, 0, 0, 1.f, 0, dbg.assemble_only ? nullptr : order, rescue_status, io.controls64, io.states64};
+  // (the references go to every launch of the solve, the rescue pass included: it solves the same problem again)
+  bmpc::WarmArgs warm = {nullptr, 0, 0, 0, 1.f, 0, dbg.assemble_only ? nullptr : order, rescue_status, io.controls64, io.states64,
+                         io.x_ref, io.foot_ref};
   if (hd->warm_on && !dbg.assemble_only && !rescue_status) {   // (a rescue pass starts cold: the stored state is the dense family's)
     const size_t need = (size_t)B * warm_per_inst;
     if (need > hd->warm.n) hd->warm_valid = false;          // growing the buffer loses the stored state
@@ -465,12 +474,12 @@ int check_batch(bmpc_handle h, int B) {
   return B > 0 ? 1 : BMPC_OK;
 }
 
-// check_batch and the arrays a solve cannot do without
+// check_batch and the arrays a solve cannot do without (foot: unless foot_ref takes its place)
 int check_common(bmpc_handle h, int B, const void* x_fb, const void* foot, const void* contact, const void* phase,
-                 const void* controls) {
+                 const void* controls, const void* foot_ref = nullptr) {
   const int rc = check_batch(h, B);
-  if (rc > 0 && (!x_fb || !foot || !contact || !phase || !controls))
-    return fail(BMPC_ERR_INVALID, "x_fb, foot, contact, phase and controls must be non-null");
+  if (rc > 0 && (!x_fb || !(foot || foot_ref) || !contact || !phase || !controls))
+    return fail(BMPC_ERR_INVALID, "x_fb, foot (or foot_ref), contact, phase and controls must be non-null");
   return rc;
 }
 
@@ -479,7 +488,7 @@ int check_common(bmpc_handle h, int B, const void* x_fb, const void* foot, const
 //  out in chunks records ev0 before its first kernel and ev1 after its last, so bmpc_last_kernel_ms spans them all)
 int solve_device_ordered(bmpc_handle h, int B, const SolveIO& io, void* stream, const int32_t* order, int ev = 3) {
   const void* controls = io.controls64 ? static_cast<const void*>(io.controls64) : static_cast<const void*>(io.controls);
-  if (int rc = check_common(h, B, io.x_fb, io.foot, io.contact, io.phase, controls); rc <= 0) return rc;
+  if (int rc = check_common(h, B, io.x_fb, io.foot, io.contact, io.phase, controls, io.foot_ref); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = pick_stream(h, stream);
   bmpc::DebugOut dbg = {nullptr, nullptr, nullptr, nullptr, h->prof_dev, 0};
@@ -535,7 +544,8 @@ int bail(bmpc_handle h, int issued, int code) {
   } while (0)
 
 // The arrays of instances lo.. in packed blocks `in` / `out` laid out by L, but for controls and states (f32 or f64)
-SolveIO packed_io(const PackedLayout& L, const char* in, char* out, size_t lo, size_t H, bool x_cmd, bool mu) {
+SolveIO packed_io(const PackedLayout& L, const char* in, char* out, size_t lo, size_t H, bool x_cmd, bool mu, bool x_ref = false,
+                  bool foot_ref = false) {
   SolveIO io;
   io.x_fb = reinterpret_cast<const float*>(in + L.i_xfb) + lo * 12;
   io.foot = reinterpret_cast<const float*>(in + L.i_foot) + lo * 6;
@@ -543,6 +553,8 @@ SolveIO packed_io(const PackedLayout& L, const char* in, char* out, size_t lo, s
   io.phase = reinterpret_cast<const int32_t*>(in + L.i_phase) + lo;
   if (x_cmd) io.x_cmd = reinterpret_cast<const float*>(in + L.i_xcmd) + lo * 12;
   if (mu) io.mu = reinterpret_cast<const float*>(in + L.i_mu) + lo * H * 2;
+  if (x_ref) io.x_ref = reinterpret_cast<const float*>(in + L.i_xref) + lo * H * 12;
+  if (foot_ref) io.foot_ref = reinterpret_cast<const float*>(in + L.i_fref) + lo * H * 6;
   io.iters = reinterpret_cast<int32_t*>(out + L.o_it) + lo;
   io.resid = reinterpret_cast<float*>(out + L.o_rs) + lo * 2;
   io.status = reinterpret_cast<int32_t*>(out + L.o_st) + lo;
@@ -564,8 +576,8 @@ SolveIO packed_io(const PackedLayout& L, const char* in, char* out, size_t lo, s
 template <typename T>
 int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact, const int32_t* phase,
                const float* x_cmd, const float* mu, T* controls, T* states, int32_t* iters, float* residuals, int32_t* status,
-               int32_t* nfactor) {
-  if (int rc = check_common(h, B, x_fb, foot, contact, phase, controls); rc <= 0) return rc;
+               int32_t* nfactor, const float* x_ref = nullptr, const float* foot_ref = nullptr) {
+  if (int rc = check_common(h, B, x_fb, foot, contact, phase, controls, foot_ref); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B, H = (size_t)h->dev.h;
   const bool timing = h->host_timing;                                 // (diagnostics: where a host-pointer call spends its time)
@@ -577,7 +589,7 @@ int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const
   struct Chunk { PackedLayout L; size_t in, out; } ck[bmpc_handle_s::HOST_CHUNKS];
   size_t in_bytes = 0, out_bytes = 0;
   for (int c = 0; c < plan.n; ++c) {
-    ck[c] = {packed_layout(plan.nb[c], H, x_cmd, mu, states, 16, 4), in_bytes, out_bytes};
+    ck[c] = {packed_layout(plan.nb[c], H, x_cmd, mu, states, 16, 4, x_ref, foot_ref), in_bytes, out_bytes};
     in_bytes += ck[c].L.in_bytes;
     out_bytes += ck[c].L.out_bytes;
   }
@@ -595,16 +607,19 @@ int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const
     char* pin = h->pin_in.p + ck[c].in;
     char* din = h->dev_in.p + ck[c].in;
     std::memcpy(pin + L.i_xfb, x_fb + lo * 12, nb * 12 * 4);
-    std::memcpy(pin + L.i_foot, foot + lo * 6, nb * 6 * 4);
+    if (foot) std::memcpy(pin + L.i_foot, foot + lo * 6, nb * 6 * 4);
     std::memcpy(pin + L.i_phase, phase + lo, nb * 4);
     if (x_cmd) std::memcpy(pin + L.i_xcmd, x_cmd + lo * 12, nb * 12 * 4);
     if (mu) std::memcpy(pin + L.i_mu, mu + lo * H * 2, nb * H * 2 * 4);
     std::memcpy(pin + L.i_con, contact + lo * H * 2, nb * H * 2);
+    if (x_ref) std::memcpy(pin + L.i_xref, x_ref + lo * H * 12, nb * H * 12 * 4);
+    if (foot_ref) std::memcpy(pin + L.i_fref, foot_ref + lo * H * 6, nb * H * 6 * 4);
     hipStream_t st = h->cstream[c];
     issued = c + 1;
     CHUNK_TRY(hipMemcpyAsync(din, pin, L.in_bytes, hipMemcpyHostToDevice, st));
     char* dout = h->dev_out.p + ck[c].out;
-    SolveIO io = packed_io(L, din, dout, 0, H, x_cmd, mu);
+    SolveIO io = packed_io(L, din, dout, 0, H, x_cmd, mu, x_ref, foot_ref);
+    if (!foot) io.foot = nullptr;               // (foot_ref given: the kernels never read foot)
     io.controls = reinterpret_cast<float*>(dout + L.o_u);
     if (states) io.states = reinterpret_cast<float*>(dout + L.o_s);
     if (int rc = solve_device_ordered(h, (int)nb, io, st, h->order, plan.events(c)); rc != BMPC_OK) return bail(h, issued, rc);
@@ -848,6 +863,17 @@ int bmpc_solve_batch_device(bmpc_handle h, int B, const float* x_fb, const float
   return solve_device_ordered(h, B, io, stream, h->order);
 }
 
+int bmpc_solve_inputs_device(bmpc_handle h, int B, const bmpc_inputs* in, float* controls, float* states, int32_t* iters,
+                             float* residuals, int32_t* status, int32_t* nfactor, void* stream) {
+  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
+  if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
+  SolveIO io;
+  io.x_fb = in->x_fb; io.foot = in->foot; io.contact = in->contact; io.phase = in->phase; io.x_cmd = in->x_cmd; io.mu = in->mu;
+  io.x_ref = in->x_ref; io.foot_ref = in->foot_ref;
+  io.controls = controls; io.states = states; io.iters = iters; io.resid = residuals; io.status = status; io.nfactor = nfactor;
+  return solve_device_ordered(h, B, io, stream, h->order);
+}
+
 int bmpc_host_io(bmpc_handle h, int B, int with_x_cmd, int with_mu, int with_states, bmpc_host_views* out) {
   if (!h || !out) return fail(BMPC_ERR_INVALID, "null argument");
   if (B < 1 || B > h->max_batch) return fail(BMPC_ERR_INVALID, "batch %d outside [1, max_batch=%d]", B, h->max_batch);
@@ -938,6 +964,14 @@ int bmpc_solve_batch_f64(bmpc_handle h, int B, const float* x_fb, const float* f
   return solve_host<double>(h, B, x_fb, foot, contact, phase, x_cmd, mu, controls, states, iters, residuals, status, nfactor);
 }
 
+int bmpc_solve_inputs_f64(bmpc_handle h, int B, const bmpc_inputs* in, double* controls, double* states, int32_t* iters,
+                          float* residuals, int32_t* status, int32_t* nfactor) {
+  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
+  if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
+  return solve_host<double>(h, B, in->x_fb, in->foot, in->contact, in->phase, in->x_cmd, in->mu, controls, states, iters, residuals,
+                            status, nfactor, in->x_ref, in->foot_ref);
+}
+
 int bmpc_synchronize(bmpc_handle h) {
   if (!h) return fail(BMPC_ERR_INVALID, "null handle");
   HIP_TRY(hipSetDevice(h->device));
@@ -948,17 +982,24 @@ int bmpc_synchronize(bmpc_handle h) {
   return BMPC_OK;
 }
 
-int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
-                        const int32_t* phase, const float* x_cmd, const float* mu, double* x_ref, double* foot_ref,
-                        double* Gt, double* qt) {
+int bmpc_debug_assemble_inputs(bmpc_handle h, int B, const bmpc_inputs* in, double* x_ref, double* foot_ref, double* Gt,
+                               double* qt) {
+  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
+  if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
+  const float *x_fb = in->x_fb, *foot = in->foot, *x_cmd = in->x_cmd, *mu = in->mu, *xr_in = in->x_ref, *fr_in = in->foot_ref;
+  const uint8_t* contact = in->contact;
+  const int32_t* phase = in->phase;
   float dummy = 0;
-  if (int rc = check_common(h, B, x_fb, foot, contact, phase, &dummy); rc <= 0) return rc;
+  if (int rc = check_common(h, B, x_fb, foot, contact, phase, &dummy, fr_in); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B, H = (size_t)h->dev.h, NW = 6 * H;
-  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->foot.ensure(n * 6)); HIP_TRY(h->contact.ensure(n * H * 2));
+  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->contact.ensure(n * H * 2));
   HIP_TRY(h->phase.ensure(n)); HIP_TRY(h->controls.ensure(n * H * 12));
+  if (foot) HIP_TRY(h->foot.ensure(n * 6));
   if (x_cmd) HIP_TRY(h->x_cmd.ensure(n * 12));
   if (mu) HIP_TRY(h->mu.ensure(n * H * 2));
+  if (xr_in) HIP_TRY(h->x_ref.ensure(n * H * 12));
+  if (fr_in) HIP_TRY(h->foot_ref.ensure(n * H * 6));
   // only what the caller asked for is formed: Gt alone is n (6h)^2 doubles (1.9 GB at B = 4096, h = 40), and the Gt / qt
   // views exist on the dense family only (h <= 20) -- a caller that wants the references gets them at every horizon
   if ((Gt || qt) && !dense_horizon(h->dev.h))
@@ -969,16 +1010,21 @@ int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* fo
   hipStream_t st = h->stream;
   HIP_TRY(hipMemsetAsync(h->dbg.p, 0, tot * sizeof(double), st));
   HIP_TRY(hipMemcpyAsync(h->x_fb.p, x_fb, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->foot.p, foot, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (foot) HIP_TRY(hipMemcpyAsync(h->foot.p, foot, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(h->contact.p, contact, n * H * 2, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(h->phase.p, phase, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
   if (x_cmd) HIP_TRY(hipMemcpyAsync(h->x_cmd.p, x_cmd, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
   if (mu) HIP_TRY(hipMemcpyAsync(h->mu.p, mu, n * H * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (xr_in) HIP_TRY(hipMemcpyAsync(h->x_ref.p, xr_in, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (fr_in) HIP_TRY(hipMemcpyAsync(h->foot_ref.p, fr_in, n * H * 6 * sizeof(float), hipMemcpyHostToDevice, st));
   bmpc::DebugOut dbg = {h->dbg.p + o_xr, h->dbg.p + o_fr, Gt ? h->dbg.p + o_gt : nullptr, qt ? h->dbg.p + o_qt : nullptr, nullptr, 1};
   SolveIO io;
-  io.x_fb = h->x_fb.p; io.foot = h->foot.p; io.contact = h->contact.p; io.phase = h->phase.p; io.controls = h->controls.p;
+  io.x_fb = h->x_fb.p; io.contact = h->contact.p; io.phase = h->phase.p; io.controls = h->controls.p;
+  if (foot) io.foot = h->foot.p;
   if (x_cmd) io.x_cmd = h->x_cmd.p;
   if (mu) io.mu = h->mu.p;
+  if (xr_in) io.x_ref = h->x_ref.p;
+  if (fr_in) io.foot_ref = h->foot_ref.p;
   if (int rc = launch(h, B, io, dbg, st, nullptr); rc != BMPC_OK) return rc;
   if (x_ref) HIP_TRY(hipMemcpyAsync(x_ref, h->dbg.p + o_xr, n * H * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
   if (foot_ref) HIP_TRY(hipMemcpyAsync(foot_ref, h->dbg.p + o_fr, n * H * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -986,6 +1032,13 @@ int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* fo
   if (qt) HIP_TRY(hipMemcpyAsync(qt, h->dbg.p + o_qt, n * NW * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return BMPC_OK;
+}
+
+int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
+                        const int32_t* phase, const float* x_cmd, const float* mu, double* x_ref, double* foot_ref,
+                        double* Gt, double* qt) {
+  const bmpc_inputs in = {x_fb, foot, contact, phase, x_cmd, mu, nullptr, nullptr};
+  return bmpc_debug_assemble_inputs(h, B, &in, x_ref, foot_ref, Gt, qt);
 }
 
 static bmpc::LowLevelParams ll_params(const bmpc_params& p) {

@@ -150,6 +150,12 @@ struct WarmArgs {
   // no device-to-host copy and no widening pass after the kernel.
   double* controls64;
   double* states64;
+  // supplied references or null (each on its own): x_ref [B][H][12] (row j = x_ref[0:12, j] of REF:61-70, the row of ones
+  // implied) and foot_ref [B][H][6] (row j = foot_ref[:, j] of REF:72-109), f32.  Phase A reads them in place of the
+  // generators; they drive the linearisation, the lever arms and the cost targets (step 0 included), nothing else -- the
+  // free response and the body axes of the line-foot rows stay those of x_fb.
+  const float* x_ref;
+  const float* foot_ref;
 };
 
 template <int H>
@@ -569,15 +575,27 @@ solve_body(const DevParams& P, const int B,
     xc[i] = x_cmd ? (RT)x_cmd[(size_t)inst * 12 + i] : (RT)P.x_cmd[i];
   }
   const int kph = phase[inst];
-  RT xr[12];                                   // x_ref[:, j]  (REF:61-70)
+  const bool lead = real && c == 0 && hf == 0;   // one lane per step
+  // A supplied reference is read by every lane of its step (one row, the same addresses: a broadcast; reading it on the lead
+  // lane alone, the only one that stores what is formed from it, cost h = 20 a fifth spilled register); the test is on a
+  // kernel argument, so the branch is uniform.
+  RT xr[12];                                   // x_ref[:, j]  (REF:61-70), or the caller's (WarmArgs::x_ref)
+  if (warm.x_ref) {
 #pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    if (j == 0) xr[i] = xfb[i];
-    else if (i < 6) xr[i] = (xc[i + 6] != (RT)0) ? xfb[i] + xc[i + 6] * ((RT)j * dt) : xc[i];
-    else xr[i] = xc[i];
+    for (int i = 0; i < 12; ++i) xr[i] = (RT)warm.x_ref[((size_t)inst * H + j) * 12 + i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      if (j == 0) xr[i] = xfb[i];
+      else if (i < 6) xr[i] = (xc[i + 6] != (RT)0) ? xfb[i] + xc[i + 6] * ((RT)j * dt) : xc[i];
+      else xr[i] = xc[i];
+    }
   }
-  RT fr[6];                                    // foot_ref[:, j]  (REF:72-109)
-  {
+  RT fr[6];                                    // foot_ref[:, j]  (REF:72-109), or the caller's (WarmArgs::foot_ref)
+  if (warm.foot_ref) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) fr[i] = (RT)warm.foot_ref[((size_t)inst * H + j) * 6 + i];
+  } else {
     const int c0 = contact[(size_t)inst * H * 2 + 0], c1 = contact[(size_t)inst * H * 2 + 1];
     const bool single = (c0 + c1) == 1;        // REF:102
     const int kk = kph % P.half;               // REF:101
@@ -591,7 +609,6 @@ solve_body(const DevParams& P, const int B,
       fr[0] = fx; fr[1] = fy; fr[2] = 0; fr[3] = fx; fr[4] = fy; fr[5] = 0;
     }
   }
-  const bool lead = real && c == 0 && hf == 0;   // one lane per step
   if (lead) {                                  // debug views of the references (tests)
     if (dbg.x_ref) {
 #pragma unroll
@@ -635,9 +652,15 @@ solve_body(const DevParams& P, const int B,
         for (int a = 0; a < 3; ++a) sm.rr[j][ft][a] = fr[3 * ft + a] - xr[3 + a];         // REF:174-175
     }
     if (l == 0) {
-      // Step 0's reference IS the feedback state (REF:63): its sines and cosines are the ones eul2rotm(x_fb[0:3]) needs for the
-      // body axes of the line-foot rows (REF:124-138, 193: roll = x[0], pitch = x[1], yaw = x[2]) -- three f64 sincos every lane
-      // used to repeat in front of the first factorisation.  Parked in the first row of Gu until phase B forms the rows.
+      // Step 0's generated reference IS the feedback state (REF:63): its sines and cosines are the ones eul2rotm(x_fb[0:3]) needs
+      // for the body axes of the line-foot rows (REF:124-138, 193: roll = x[0], pitch = x[1], yaw = x[2]) -- three f64 sincos every
+      // lane used to repeat in front of the first factorisation.  Parked in the first row of Gu until phase B forms the rows.
+      // A supplied x_ref says nothing about the body axes: they are then formed from x_fb here, by this lane alone.
+      if (warm.x_ref) {
+        sincos(xfb[0], &sy, &cy);
+        sincos(xfb[1], &sp, &cp);
+        sincos(xfb[2], &sr, &cr);
+      }
       sm.Gu[0][0] = sy; sm.Gu[0][1] = cy; sm.Gu[0][2] = sp; sm.Gu[0][3] = cp; sm.Gu[0][4] = sr; sm.Gu[0][5] = cr;
     }
   }

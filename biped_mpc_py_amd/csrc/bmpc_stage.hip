@@ -178,6 +178,7 @@ struct alignas(16) StageSmem {
   RT Gu[6][6];
   RT GuT[6][6];
   float eyz[6];
+  const float* xref;               // WarmArgs::x_ref for the outputs: parked here, not kept in SGPRs across the iterations
 };
 
 // x with S x = b for a 6x6 SPD S given by its lower triangle (LDL', f32; every lane for itself)
@@ -346,17 +347,30 @@ stage_body(const DevParams& P, const int B,
     for (int s = 0; s < NP; ++s) {
       const int j = jg[s];
       const Step jst = BMPC_STEP(s);
-      RT xr[12];                               // x_ref[:, j]  (REF:61-70)
+      // x_ref[:, j]  (REF:61-70), or the caller's (WarmArgs::x_ref; the tests are on kernel arguments: uniform branches).  Every
+      // lane of the step needs the Euler angles (R_inv), the lead lane the position too; the coordinate of the lane's own
+      // scans is read on its own below.
+      RT xr[12];
+      if (warm.x_ref) {
 #pragma unroll
-      for (int i = 0; i < 12; ++i) {
-        if (j == 0) xr[i] = xfb[i];
-        else if (i < 6) xr[i] = (xc[i + 6] != (RT)0) ? xfb[i] + xc[i + 6] * ((RT)j * dt) : xc[i];
-        else xr[i] = xc[i];
+        for (int i = 0; i < 12; ++i) xr[i] = (RT)warm.x_ref[((size_t)inst * H + j) * 12 + i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+          if (j == 0) xr[i] = xfb[i];
+          else if (i < 6) xr[i] = (xc[i + 6] != (RT)0) ? xfb[i] + xc[i + 6] * ((RT)j * dt) : xc[i];
+          else xr[i] = xc[i];
+        }
       }
-      RT fr[6];                                // foot_ref[:, j]  (REF:72-109)
+      RT fr[6];                                // foot_ref[:, j]  (REF:72-109), or the caller's (WarmArgs::foot_ref)
+      if (warm.foot_ref) {
 #pragma unroll
-      for (int i = 0; i < 6; ++i) fr[i] = (RT)foot[(size_t)inst * 6 + i];
-      if (single && j >= P.half - kk) {
+        for (int i = 0; i < 6; ++i) fr[i] = (RT)warm.foot_ref[((size_t)inst * H + j) * 6 + i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) fr[i] = (RT)foot[(size_t)inst * 6 + i];
+      }
+      if (!warm.foot_ref && single && j >= P.half - kk) {
         const bool second = j >= 2 * P.half - kk;
         const RT hor = second ? (RT)0.5 * (RT)H * dt : (RT)0.5 * (RT)H / (RT)2 * dt;   // REF:74, 78
         const RT fx = xfb[3] + xfb[9] * hor + (RT)P.kv * (xfb[3] - xc[3]);
@@ -404,7 +418,8 @@ stage_body(const DevParams& P, const int B,
       }
       // coordinate n of x_ref[:, j], and the term of the free response that is a sum over the steps:
       // euler_j = euler_fb + dt sum_{i <= j} Rinv_i omega_fb  (the other coordinates are closed forms)
-      const RT xrn = (j == 0) ? xfb_n : ((n < 6 && xc_n6 != (RT)0) ? xfb_n + xc_n6 * ((RT)j * dt) : xc_n);
+      const RT xrn = warm.x_ref ? (RT)warm.x_ref[((size_t)inst * H + j) * 12 + n]
+                                : (j == 0) ? xfb_n : ((n < 6 && xc_n6 != (RT)0) ? xfb_n + xc_n6 * ((RT)j * dt) : xc_n);
       RT rw = 0;
       if (n < 3) rw = dt * ((n == 0 ? Rv[0] : (n == 1 ? Rv[3] : Rv[6])) * xfb[6] + (n == 0 ? Rv[1] : (n == 1 ? Rv[4] : Rv[7])) * xfb[7] +
                             (n == 0 ? Rv[2] : (n == 1 ? Rv[5] : Rv[8])) * xfb[8]);
@@ -412,6 +427,7 @@ stage_body(const DevParams& P, const int B,
       e0[s] = xrn;
     }
   }
+  if (lt == 0) sm.xref = warm.x_ref;
   BMPC_WAVE_SYNC();
   prefix_incl(err);
 #pragma unroll
@@ -1701,6 +1717,7 @@ stage_body(const DevParams& P, const int B,
   }
 
   // ------------------------------------------------------------------ F. outputs (REF:300-304)
+  const float* xref = sm.xref;
   // every way out of the loop rebuilt err exactly at its last stopping test: X = x_ref + err
 #pragma unroll
   for (int s = 0; s < NP; ++s) {
@@ -1712,7 +1729,10 @@ stage_body(const DevParams& P, const int B,
     else controls[((size_t)inst * H + j) * 12 + pos] = (float)xo[s];
     if (states || warm.states64) {
       const size_t sbase = ((size_t)inst * H + j) * 13;
-      const RT xrn = (j == 0) ? xfb_n : ((n < 6 && xc_n6 != (RT)0) ? xfb_n + xc_n6 * ((RT)j * dt) : xc_n);      // x_ref[n, j]
+      // x_ref[n, j]: a supplied one is read again from HBM here rather than kept in a register across the loop (the pointer
+      // comes back from LDS; held in registers it cost the two-wave variants 4 more SGPR spills)
+      RT xrn = (j == 0) ? xfb_n : ((n < 6 && xc_n6 != (RT)0) ? xfb_n + xc_n6 * ((RT)j * dt) : xc_n);
+      if (xref) xrn = (RT)xref[((size_t)inst * H + j) * 12 + n];
       const float sv = (float)(xrn + err[s]);
       if (warm.states64) { warm.states64[sbase + n] = (double)sv; if (n == 0) warm.states64[sbase + 12] = 1.0; }
       else { states[sbase + n] = sv; if (n == 0) states[sbase + 12] = 1.0f; }

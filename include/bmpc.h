@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define BMPC_ABI_VERSION 11
+#define BMPC_ABI_VERSION 12
 
 /* `stream` arguments are hipStream_t values passed as void*.  NULL is HIP's null (legacy default)
  * stream -- what torch.cuda.current_stream().cuda_stream is when no stream context is active -- so a
@@ -305,6 +305,47 @@ int bmpc_debug_assemble(bmpc_handle h, int B,
                         const float* x_fb, const float* foot, const uint8_t* contact,
                         const int32_t* phase, const float* x_cmd, const float* mu,
                         double* x_ref, double* foot_ref, double* Gt, double* qt);
+
+/*
+ * Reference tracking (ABI 12): the inputs of a solve as one named descriptor, with what the solve tracks.  By default the kernels
+ * generate the references of REF:61-70 (constant commanded velocities from x_fb) and REF:72-109 (the foothold heuristic); a
+ * caller who tracks something else -- stairs, a crouch, a planner's footholds -- supplies them per instance:
+ *   x_ref    [B][h][12] or NULL: row j = x_ref[0:12, j] of REF:61-70 (the 13th row of ones is implied)
+ *   foot_ref [B][h][6]  or NULL: row j = foot_ref[:, j] of REF:72-109
+ * the layouts of bmpc_debug_assemble's outputs, in fp32.  Each is independent of the other; a NULL one is generated exactly as
+ * by the ABI-11 entries (which are these entries with both NULL, bit for bit).  A supplied array drives everything the generated
+ * one drives: the linearisation of step j (Rot, I_w, R_inv from x_ref[0:3, j], REF:150-164), the lever arms
+ * foot_ref[:, j] - x_ref[3:6, j] (REF:174-175) and the cost target of the state after step j (REF:282-284) -- column 0 included,
+ * used as given (the generator sets it to x_fb, REF:63).  It does not change the free response (from x_fb), the friction, box and
+ * pinned rows, or the body axes of the line-foot rows, which are those of R = eul2rotm(x_fb[0:3]) (REF:193) whatever x_ref
+ * holds.  Non-finite references, or a pitch of +-90 degrees (R_inv singular, as in the reference), give that instance
+ * status BMPC_NUMERICAL, never a failed batch.  The rescue pass solves against the same references.
+ *   bmpc_solve_inputs_f64      bmpc_solve_batch_f64 with the descriptor (host pointers, synchronous, the same chunked path)
+ *   bmpc_solve_inputs_device   bmpc_solve_batch_device with the descriptor (device pointers, asynchronous on `stream`)
+ *   bmpc_debug_assemble_inputs bmpc_debug_assemble with the descriptor: x_ref / foot_ref return the references used (a supplied
+ *                              one widened to fp64), Gt / qt the assembly built from them
+ * A NULL handle or descriptor, or foot == NULL without foot_ref, is BMPC_ERR_INVALID.  The handle's I/O block (bmpc_host_io) and
+ * bmpc_rollout_device always generate.
+ */
+typedef struct bmpc_inputs {
+  const float* x_fb;        /* [B][12] */
+  const float* foot;        /* [B][6]; may be NULL iff foot_ref != NULL (only the foothold generator reads it) */
+  const uint8_t* contact;   /* [B][h][2] */
+  const int32_t* phase;     /* [B] */
+  const float* x_cmd;       /* [B][12] or NULL -> params.x_cmd */
+  const float* mu;          /* [B][h][2] or NULL -> params.mu */
+  const float* x_ref;       /* [B][h][12] or NULL -> REF:61-70 generated */
+  const float* foot_ref;    /* [B][h][6] or NULL -> REF:72-109 generated */
+} bmpc_inputs;
+int bmpc_solve_inputs_f64(bmpc_handle h, int B, const bmpc_inputs* in,
+                          double* controls, double* states,
+                          int32_t* iters, float* residuals, int32_t* status, int32_t* nfactor);
+int bmpc_solve_inputs_device(bmpc_handle h, int B, const bmpc_inputs* in,
+                             float* controls, float* states,
+                             int32_t* iters, float* residuals, int32_t* status, int32_t* nfactor,
+                             void* stream);
+int bmpc_debug_assemble_inputs(bmpc_handle h, int B, const bmpc_inputs* in,
+                               double* x_ref, double* foot_ref, double* Gt, double* qt);
 
 /*
  * The step either side of the MPC solve, batched; HOST pointers, synchronous.
