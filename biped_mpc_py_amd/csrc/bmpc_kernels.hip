@@ -1342,11 +1342,47 @@ solve_body(const DevParams& P, const int B,
           float* nA = sm.piv[par ^ 1];
           par ^= 1;
           const int un = u + 2 < HN ? (u >> 1) + 1 : 0;  // register pair of the next pivot columns (last step of a half: the other half's first)
+          // the pivot rows are fetched in chunks of at most CH entries each (registers), the chunk with the next pivot
+          // columns (ch0) first, and (where ch0 is fetched at the barrier, below) the float4 that holds them first of all
+          constexpr int CH = HN <= 32 ? HN : 16;
+          static_assert(CH % 4 == 0 || CH == HN, "chunk of whole float4s");
+          constexpr int NCH = (HN + CH - 1) / CH;
+          const int ch0 = (2 * un) / CH;                    // (static: the loops are unrolled)
+          const int qn = (2 * un) & ~3;                     // first entry of the float4 with the next pivot columns
+          f2 pa[CH / 2], pb[CH / 2];
+          auto fetch = [&](int q, int c0i, int c1i) {       // entries q .. q + 3 (or the chunk's last two) of both pivot rows
+            if (q + 4 <= c1i) {
+              const float4 a4 = *reinterpret_cast<const float4*>(&bA[hf * HNP + q]);
+              const float4 b4 = *reinterpret_cast<const float4*>(&bB[hf * HNP + q]);
+              pa[(q - c0i) / 2] = f2{a4.x, a4.y}; pa[(q - c0i) / 2 + 1] = f2{a4.z, a4.w};
+              pb[(q - c0i) / 2] = f2{b4.x, b4.y}; pb[(q - c0i) / 2 + 1] = f2{b4.z, b4.w};
+            } else {
+              const float2 a2 = *reinterpret_cast<const float2*>(&bA[hf * HNP + q]);
+              const float2 b2 = *reinterpret_cast<const float2*>(&bB[hf * HNP + q]);
+              pa[(q - c0i) / 2] = f2{a2.x, a2.y};
+              pb[(q - c0i) / 2] = f2{b2.x, b2.y};
+            }
+          };
           sync_workgroup();
           const float2 pk = *reinterpret_cast<const float2*>(&bA[pb0 + u]);      // V[k][k], V[k + 1][k]
           const float p11 = bB[pb0 + u + 1];
           const float c0 = bA[ps], c1 = bB[ps];            // V[r][k], V[r][k + 1]
-          BMPC_SCHED_BARRIER();                            // the step's scalar loads are in flight before anything is used
+          // Chunk ch0 of the pivot rows goes out at the barrier too, behind the scalars: its latency runs under the pivot
+          // algebra below, which needs none of it (round 7; the compiler issued these reads after the algebra).  Not at
+          // h = 18: the chunk live across the algebra spills 12 registers there, so it is fetched after it, as before.
+          constexpr bool EARLY_CH0 = HN <= 48;
+          auto fetch_ch0 = [&]() {
+            const int c0i = ch0 * CH, c1i = c0i + CH < HN ? c0i + CH : HN;
+            if constexpr (EARLY_CH0) {
+              fetch(qn, c0i, c1i);
+              BMPC_SCHED_BARRIER();                        // (LDS returns in order: the publication waits for these alone)
+            }
+#pragma unroll
+            for (int q = c0i; q < c1i; q += 4)
+              if (!EARLY_CH0 || q != qn) fetch(q, c0i, c1i);
+          };
+          if constexpr (EARLY_CH0) fetch_ch0();
+          BMPC_SCHED_BARRIER();                            // the step's loads are in flight before anything is used
           const float id = rcp_approx(pk.x * p11 - pk.y * pk.y);
           const float q00 = p11 * id, q01 = -pk.y * id, q11 = pk.x * id;  // P^-1
           qmax = fmaxf(qmax, fmaxf(q00, q11));             // (pivot check: see the rotating form)
@@ -1356,42 +1392,31 @@ solve_body(const DevParams& P, const int B,
           t0 = is0 ? 1.f - q00 : (is1 ? -q01 : t0);
           t1 = is0 ? -q01 : (is1 ? 1.f - q11 : t1);
           const f2 m0 = {-t0, -t0}, m1 = {-t1, -t1};
-          // the pivot rows are fetched in chunks of at most CH entries each (registers), the chunk with the next pivot
-          // columns first: they are updated first and published at once, so that their round trip overlaps with the rest
-          constexpr int CH = HN <= 32 ? HN : 16;
-          static_assert(CH % 4 == 0 || CH == HN, "chunk of whole float4s");
-          constexpr int NCH = (HN + CH - 1) / CH;
-          const int ch0 = (2 * un) / CH;                    // (static: the loops are unrolled)
+          if constexpr (!EARLY_CH0) fetch_ch0();
+          // The next pivot columns are updated first and published at once; the scheduling barrier behind the store keeps
+          // the compiler from sinking it behind the step's other FMAs (it did, to the last one: the whole round trip then
+          // sat in front of the s_barrier), so that its round trip runs under them.
+          {
+            const int c0i = ch0 * CH;
+            Vr[un] = __builtin_elementwise_fma(m1, pb[un - c0i / 2], __builtin_elementwise_fma(m0, pa[un - c0i / 2], Vr[un]));
+            const int wn = u + 2 < HN ? wsh : wso;         // (after the very last step: columns nobody reads)
+            nA[wn] = Vr[un].x;
+            nA[PVS + wn] = Vr[un].y;
+          }
+          if constexpr (EARLY_CH0) BMPC_SCHED_BARRIER();
 #pragma unroll
           for (int cc = 0; cc < NCH; ++cc) {
-            const int ci = cc == 0 ? ch0 : (cc <= ch0 ? cc - 1 : cc);       // chunk ch0 first, the others in order
+            const int ci = cc == 0 ? ch0 : (cc <= ch0 ? cc - 1 : cc);       // chunk ch0 (fetched above) first, the others in order
             const int c0i = ci * CH;
             const int c1i = c0i + CH < HN ? c0i + CH : HN;
-            f2 pa[CH / 2], pb[CH / 2];
+            if (cc > 0) {
+              BMPC_FENCE();
 #pragma unroll
-            for (int q = c0i; q < c1i; q += 4) {
-              if (q + 4 <= c1i) {
-                const float4 a4 = *reinterpret_cast<const float4*>(&bA[hf * HNP + q]);
-                const float4 b4 = *reinterpret_cast<const float4*>(&bB[hf * HNP + q]);
-                pa[(q - c0i) / 2] = f2{a4.x, a4.y}; pa[(q - c0i) / 2 + 1] = f2{a4.z, a4.w};
-                pb[(q - c0i) / 2] = f2{b4.x, b4.y}; pb[(q - c0i) / 2 + 1] = f2{b4.z, b4.w};
-              } else {
-                const float2 a2 = *reinterpret_cast<const float2*>(&bA[hf * HNP + q]);
-                const float2 b2 = *reinterpret_cast<const float2*>(&bB[hf * HNP + q]);
-                pa[(q - c0i) / 2] = f2{a2.x, a2.y};
-                pb[(q - c0i) / 2] = f2{b2.x, b2.y};
-              }
-            }
-            if (cc == 0) {
-              Vr[un] = __builtin_elementwise_fma(m1, pb[un - c0i / 2], __builtin_elementwise_fma(m0, pa[un - c0i / 2], Vr[un]));
-              const int wn = u + 2 < HN ? wsh : wso;         // (after the very last step: columns nobody reads)
-              nA[wn] = Vr[un].x;
-              nA[PVS + wn] = Vr[un].y;
+              for (int q = c0i; q < c1i; q += 4) fetch(q, c0i, c1i);
             }
 #pragma unroll
             for (int r = c0i / 2; r < c1i / 2; ++r)
               if (r != un) Vr[r] = __builtin_elementwise_fma(m1, pb[r - c0i / 2], __builtin_elementwise_fma(m0, pa[r - c0i / 2], Vr[r]));
-            if (cc + 1 < NCH) BMPC_FENCE();
           }
           if (hf == hh) Vr[u >> 1] = is0 ? f2{-q00, -q01} : (is1 ? f2{-q01, -q11} : f2{t0, t1});
         }
