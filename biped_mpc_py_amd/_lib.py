@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbmpc.so")
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # every symbol include/bmpc.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = (
@@ -20,6 +20,7 @@ EXPORTS = (
     "bmpc_host_io", "bmpc_solve_batch_io", "bmpc_host_io_generation",
     "bmpc_debug_assemble", "bmpc_debug_set_profile", "bmpc_last_kernel_ms",
     "bmpc_solve_inputs_f64", "bmpc_solve_inputs_device", "bmpc_debug_assemble_inputs",
+    "bmpc_evaluate_device", "bmpc_evaluate",
     "bmpc_foot_position_world", "bmpc_foot_position_world_device",
     "bmpc_low_level_control", "bmpc_low_level_control_device",
     "bmpc_gait_default", "bmpc_contact_sequence", "bmpc_contact_sequence_device",
@@ -41,6 +42,11 @@ class CHostViews(C.Structure):
 class CInputs(C.Structure):
     """`bmpc_inputs` of include/bmpc.h: the inputs of a solve, supplied references included (NULL: generated)."""
     _fields_ = [(n, C.c_void_p) for n in ("x_fb", "foot", "contact", "phase", "x_cmd", "mu", "x_ref", "foot_ref")]
+
+
+class CEvalOut(C.Structure):
+    """`bmpc_eval_out` of include/bmpc.h: the outputs of an evaluation, each optional (NULL: not wanted)."""
+    _fields_ = [(n, C.c_void_p) for n in ("cost", "objective", "states", "violation")]
 
 
 class BmpcError(RuntimeError):
@@ -132,6 +138,8 @@ def load():
     lib.bmpc_solve_inputs_f64.argtypes = [vp, ip, C.POINTER(CInputs)] + [vp] * 6
     lib.bmpc_solve_inputs_device.argtypes = [vp, ip, C.POINTER(CInputs)] + [vp] * 6 + [vp]
     lib.bmpc_debug_assemble_inputs.argtypes = [vp, ip, C.POINTER(CInputs)] + [vp] * 4
+    lib.bmpc_evaluate_device.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CEvalOut), vp]
+    lib.bmpc_evaluate.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CEvalOut)]
     lib.bmpc_foot_position_world.argtypes = [vp, ip, vp, vp, vp]
     lib.bmpc_foot_position_world_device.argtypes = [vp, ip, vp, vp, vp, vp]
     lib.bmpc_low_level_control.argtypes = [vp, ip] + [vp] * 8

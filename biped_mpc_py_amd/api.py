@@ -66,10 +66,11 @@ def get_contact_sequence(t, mpc, half=None):
     return np.stack([leg0, ~leg0], axis=1).astype(int)
 
 
-def _kernel_refs(x_ref, foot_ref, B, h):
+def _kernel_refs(x_ref, foot_ref, B, h, finite=True):
     """Supplied references in the kernel layout -- x_ref (B,h,12), foot_ref (B,h,6), each or None -- as C-contiguous fp32 arrays
     (what `bmpc_inputs` takes).  Raises ValueError on a wrong shape or a non-finite value: a bad reference is the caller's
-    mistake, caught before the call (on the device it would only show as status 2 of that instance)."""
+    mistake, caught before the call (on the device it would only show as status 2 of that instance).  `finite=False` (the
+    evaluation, whose answer for such an instance is defined: NaN) leaves the values unchecked."""
     out = []
     for name, a, w in (("x_ref", x_ref, 12), ("foot_ref", foot_ref, 6)):
         if a is None:
@@ -78,7 +79,7 @@ def _kernel_refs(x_ref, foot_ref, B, h):
         a = np.asarray(a)
         if a.shape != (B, h, w):
             raise ValueError(f"{name} must have shape ({B}, {h}, {w}) (kernel layout: row j = step j), got {a.shape}")
-        if not np.all(np.isfinite(a)):
+        if finite and not np.all(np.isfinite(a)):
             raise ValueError(f"{name} holds non-finite values")
         out.append(np.ascontiguousarray(a, np.float32))
     return out[0], out[1]
@@ -109,6 +110,16 @@ def references_to_kernel_layout(x_ref=None, foot_ref=None, h=None):
             raise ValueError("foot_ref holds non-finite values")
         fr = np.ascontiguousarray(np.swapaxes(a, -1, -2))
     return xr, fr
+
+
+def _controls_f32(controls, h, B=None):
+    """A control sequence as the evaluation takes it: (B,h,12) of any float dtype -> C-contiguous fp32.  Shape checked here
+    (ValueError), before any call."""
+    c = np.asarray(controls)
+    if c.ndim != 3 or c.shape[1:] != (h, 12) or (B is not None and c.shape[0] != B) or not np.issubdtype(c.dtype, np.floating):
+        raise ValueError(f"controls must be a float array of shape ({'B' if B is None else B}, {h}, 12) (row k = [f1 f2 m1 m2]), "
+                         f"got {c.dtype} {c.shape}")
+    return np.ascontiguousarray(c, np.float32)
 
 
 def _ptr(a):
@@ -183,13 +194,16 @@ class BatchSolver:
             mu = np.ascontiguousarray(np.asarray(mu, np.float32).reshape(B, h, 2))
         return B, x_fb, foot, contact, phase, x_cmd, mu
 
-    def solve(self, x_fb, foot, contact, phase, x_cmd=None, mu=None, want_states=True, out=None, x_ref=None, foot_ref=None):
+    def solve(self, x_fb, foot, contact, phase, x_cmd=None, mu=None, want_states=True, out=None, x_ref=None, foot_ref=None,
+              evaluate=False):
         """Host arrays in, host arrays out (fp32 over PCIe, fp64 returned -- the reference's dtype, REF:300-304; the
         widening happens inside `bmpc_solve_batch_f64` while the results are unpacked, overlapped with the solve).  Returns
         (states (B,h,13) | None, controls (B,h,12), info).  `out`: optional (states | None, controls) fp64 C-contiguous
         arrays of those shapes to write into (a control loop reuses its buffers instead of allocating 8 MB per call).
         `x_ref` (B,h,12) / `foot_ref` (B,h,6): references to track instead of the generated ones (`bmpc_solve_inputs_f64`,
-        include/bmpc.h; kernel layout, row j = step j); `foot` may then be None if `foot_ref` is given."""
+        include/bmpc.h; kernel layout, row j = step j); `foot` may then be None if `foot_ref` is given.
+        `evaluate=True`: `info` gains `cost` (B,), `objective` (B,), `violation` (B,4) of the returned controls (those of the rescue
+        pass where it ran), as `evaluate` gives them; by default `info` keeps exactly its four keys."""
         B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
         x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h)
         if foot is None and foot_ref is None:
@@ -220,7 +234,35 @@ class BatchSolver:
             _lib.check(self._lib.bmpc_solve_inputs_f64(
                 self._h, B, C.byref(inp), _ptr(controls), _ptr(states), _ptr(iters), _ptr(resid), _ptr(status), _ptr(nfactor)))
         info = dict(iters=iters, status=status, nfactor=nfactor, residuals=resid)
+        if evaluate:
+            ev = self.evaluate(x_fb, foot, contact, phase, controls, x_cmd=x_cmd, mu=mu, x_ref=x_ref, foot_ref=foot_ref)
+            info.update(cost=ev["cost"], objective=ev["objective"], violation=ev["violation"])
         return states, controls, info
+
+    def evaluate(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None, want_states=False):
+        """What the MPC's own model makes of GIVEN control sequences (`bmpc_evaluate`, include/bmpc.h): inputs as `solve` takes
+        them (references in the kernel layout, generated where None) and `controls` (B,h,12), row k = [f1 f2 m1 m2] -- the
+        solver's own, a warm-start guess, a policy's output, another solver's answer.  Returns dict(cost (B,), objective (B,),
+        violation (B,4), states (B,h,13) | None), NumPy fp64: the cost REF:278-286 minimises completed to a sum of squares (>= 0: the
+        number to rank samples by), the value 1/2 z'Pz + q'z the reference hands its solver, the largest violation per row class
+        [friction pyramid, force box, moment box, line foot] (0: the class holds) and the predicted states X(U).
+        `controls` may have any float dtype and is converted to fp32, which is what the kernel reads; a solve's fp64 `controls` ARE
+        fp32 values (widened exactly), so they pass through unchanged.  Its shape is checked before the call (ValueError).  An
+        instance with a non-finite entry anywhere, or a reference pitch of +-90 degrees, gets NaN in all its outputs (reference
+        values are therefore not checked here); no other instance is touched."""
+        c32 = _controls_f32(controls, self.h)
+        B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
+        if c32.shape[0] != B:
+            raise ValueError(f"controls must have shape ({B}, {self.h}, 12), got {c32.shape}")
+        x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h, finite=False)
+        if foot is None and foot_ref is None:
+            raise ValueError("foot is required unless foot_ref is given")
+        res = dict(cost=np.empty(B, np.float64), objective=np.empty(B, np.float64), violation=np.empty((B, 4), np.float64),
+                   states=np.empty((B, self.h, 13), np.float64) if want_states else None)
+        inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
+        eo = _lib.CEvalOut(_ptr(res["cost"]), _ptr(res["objective"]), _ptr(res["states"]), _ptr(res["violation"]))
+        _lib.check(self._lib.bmpc_evaluate(self._h, B, C.byref(inp), _ptr(c32), C.byref(eo)))
+        return res
 
     def _io_views(self, B, with_x_cmd, with_mu, with_states):
         """NumPy views of the handle's page-locked I/O block laid out for batches of B (`bmpc_host_io`); cached per layout."""
@@ -355,6 +397,43 @@ class BatchSolver:
             chk(iters, torch.int32, (B,)) or None, chk(residuals, torch.float32, (B, 2)) or None,
             chk(status, torch.int32, (B,)) or None, chk(nfactor, torch.int32, (B,)) or None, st))
         return controls, states
+
+    def evaluate_device(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None,
+                        cost=None, objective=None, violation=None, states=None, want_states=False, stream=None):
+        """`evaluate` on CUDA(HIP) torch tensors of this solver's device (`bmpc_evaluate_device`): inputs as `solve_device` takes
+        them, `controls` (B,h,12) float32 -- e.g. the tensor a `solve_device` on the same stream has just been asked to fill: no
+        synchronisation is needed in between.  Outputs are float64 tensors cost (B,), objective (B,), violation (B,4) and -- if
+        passed, or with `want_states` -- states (B,h,13), allocated where not passed.  Asynchronous on `stream` (default: torch's
+        current stream); nothing crosses PCIe.  Returns dict(cost, objective, violation, states | None)."""
+        import torch
+        B = x_fb.shape[0]
+        h = self.h
+        dev = x_fb.device
+
+        def chk(t, dtype, shape):
+            if t is None:
+                return None
+            if t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"expected contiguous {dtype} tensor of shape {shape} on {dev}")
+            return t.data_ptr()
+
+        if dev.type != "cuda" or dev.index != self.device:
+            raise ValueError(f"tensors must live on cuda:{self.device}")
+        f64 = lambda shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        cost = f64((B,)) if cost is None else cost
+        objective = f64((B,)) if objective is None else objective
+        violation = f64((B, 4)) if violation is None else violation
+        if states is None and want_states:
+            states = f64((B, h, 13))
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        inp = _lib.CInputs(chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)),
+                           chk(contact, torch.uint8, (B, h, 2)), chk(phase, torch.int32, (B,)),
+                           chk(x_cmd, torch.float32, (B, 12)), chk(mu, torch.float32, (B, h, 2)),
+                           chk(x_ref, torch.float32, (B, h, 12)), chk(foot_ref, torch.float32, (B, h, 6)))
+        eo = _lib.CEvalOut(chk(cost, torch.float64, (B,)), chk(objective, torch.float64, (B,)),
+                           chk(states, torch.float64, (B, h, 13)), chk(violation, torch.float64, (B, 4)))
+        _lib.check(self._lib.bmpc_evaluate_device(self._h, B, C.byref(inp), chk(controls, torch.float32, (B, h, 12)), C.byref(eo), st))
+        return dict(cost=cost, objective=objective, violation=violation, states=states)
 
     # ---- the step either side of the solve (SURVEY 8(f) row 1) ------------------------------------
     def foot_position_world(self, x_fb, q):
@@ -572,6 +651,38 @@ def solve_mpc(x_fb, t, foot, mpc, biped, contact, half=None, device=0, solver_op
                                        x_ref=None if x_ref is None else np.asarray(x_ref)[None],
                                        foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None])
     return states[0], controls[0]
+
+
+def evaluate_mpc_batch(x_fb, t, foot, contact, controls, mpc=None, biped=None, x_cmd=None, mu=None, phase=None, half=None,
+                       device=0, x_ref=None, foot_ref=None):
+    """What the model of REF:187-304 makes of given control sequences: `solve_mpc_batch`'s call surface (references in the
+    reference's orientation, the cached handle per horizon and device) with `controls` (B,h,12) added.  Returns
+    dict(cost (B,), objective (B,), violation (B,4), states (B,h,13)) as `BatchSolver.evaluate`."""
+    from .params import MPC
+    mpc = mpc if mpc is not None else MPC()
+    c32 = _controls_f32(controls, int(mpc.h))
+    xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
+    solver = _cached_solver(mpc, biped, half, device, None)
+    if phase is None:
+        phase = phase_indices(t, mpc.dt, mpc.h)
+    return solver.evaluate(x_fb, foot, contact, phase, c32, x_cmd=x_cmd, mu=mu, x_ref=xr, foot_ref=fr, want_states=True)
+
+
+def evaluate_mpc(x_fb, t, foot, mpc, biped, contact, controls, half=None, device=0, x_ref=None, foot_ref=None):
+    """`evaluate_mpc_batch` for one instance with `solve_mpc`'s arguments and `controls` (h,12) -- e.g. what `solve_mpc` returned.
+    Returns dict(cost float, objective float, violation (4,), states (h,13))."""
+    h = int(mpc.h)
+    c = np.asarray(controls)
+    if c.shape != (h, 12):
+        raise ValueError(f"controls must have shape ({h}, 12), got {c.shape}")
+    contact = np.asarray(contact)
+    if contact.ndim != 2 or contact.shape[1] != 2 or contact.shape[0] < h:
+        raise ValueError(f"contact must have at least {h} rows of 2 (REF:239-249 indexes contact[k] for k < h)")
+    r = evaluate_mpc_batch(np.asarray(x_fb, float).reshape(1, 12), [t], np.asarray(foot, float).reshape(1, 6), contact[None, :h, :],
+                           c[None], mpc=mpc, biped=biped, half=half, device=device,
+                           x_ref=None if x_ref is None else np.asarray(x_ref)[None],
+                           foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None])
+    return dict(cost=float(r["cost"][0]), objective=float(r["objective"][0]), violation=r["violation"][0], states=r["states"][0])
 
 
 def reference_trajectories_batch(x_fb, t, foot, contact, mpc=None, biped=None, x_cmd=None, phase=None, half=None, device=0):

@@ -4,6 +4,7 @@
 #include "bmpc_kernels.hip"
 #include "bmpc_stage.hip"
 #include "bmpc_lowlevel.hip"
+#include "bmpc_evaluate.hip"
 
 #include <chrono>
 #include <cmath>
@@ -325,7 +326,8 @@ struct bmpc_handle_s {
     bool x_cmd = false, mu = false, states = false;
   } io;
   DevBuf<float> x_fb, foot, x_cmd, mu, controls, states, resid;
-  DevBuf<float> x_ref, foot_ref;    // supplied references of bmpc_debug_assemble_inputs
+  DevBuf<float> x_ref, foot_ref;    // supplied references of bmpc_debug_assemble_inputs / bmpc_evaluate
+  DevBuf<double> eval_out;          // results of bmpc_evaluate (host pointers) on their way back
   DevBuf<uint8_t> contact;
   DevBuf<int32_t> phase, iters, status, nfactor;
   DevBuf<double> dbg;
@@ -824,6 +826,7 @@ int bmpc_destroy(bmpc_handle h) {
   if (h->cev_own) (void)hipEventDestroy(h->cev_own);
   if (h->cev_in) (void)hipEventDestroy(h->cev_in);
   h->io_states.release();
+  h->x_ref.release(); h->foot_ref.release(); h->eval_out.release();
   h->pin_in.release(); h->pin_out.release(); h->dev_in.release(); h->dev_out.release();
   h->io_in.release(); h->io_out.release(); h->io_dev.release();
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1039,6 +1042,76 @@ int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* fo
                         double* Gt, double* qt) {
   const bmpc_inputs in = {x_fb, foot, contact, phase, x_cmd, mu, nullptr, nullptr};
   return bmpc_debug_assemble_inputs(h, B, &in, x_ref, foot_ref, Gt, qt);
+}
+
+// ---- evaluation of given controls (bmpc_evaluate.hip): one launch, nothing of the handle's per-solve state involved
+
+// what both entries check before a device is touched: an error code (< 0), BMPC_OK when there is nothing to do, 1 to go on
+static int check_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out) {
+  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
+  if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
+  if (!controls) return fail(BMPC_ERR_INVALID, "null controls");
+  if (!out) return fail(BMPC_ERR_INVALID, "null bmpc_eval_out");
+  if (!out->cost && !out->objective && !out->states && !out->violation)
+    return fail(BMPC_ERR_INVALID, "bmpc_eval_out: at least one of cost, objective, states, violation must be non-null");
+  return check_common(h, B, in->x_fb, in->foot, in->contact, in->phase, controls, in->foot_ref);
+}
+
+static int launch_evaluate(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const bmpc_eval_out& out, hipStream_t st) {
+  const int hh = h->params.h;
+  const int L = hh <= 16 ? 16 : (hh <= 32 ? 32 : 64);          // lanes per instance (bmpc_evaluate.hip)
+  const long long lanes = (long long)B * L;
+  const bmpc::EvalOut o = {out.cost, out.objective, out.states, out.violation};
+  hipLaunchKernelGGL(bmpc::evaluate_kernel, dim3((unsigned)((lanes + bmpc::EVAL_NT - 1) / bmpc::EVAL_NT)), dim3(bmpc::EVAL_NT), 0, st,
+                     bmpc::eval_params(h->params, h->dev.Iinv), B, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd, in.mu, in.x_ref,
+                     in.foot_ref, controls, o);
+  HIP_TRY(hipGetLastError());
+  return BMPC_OK;
+}
+
+int bmpc_evaluate_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out, void* stream) {
+  if (int rc = check_evaluate(h, B, in, controls, out); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return launch_evaluate(h, B, *in, controls, *out, pick_stream(h, stream));
+}
+
+int bmpc_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out) {
+  if (int rc = check_evaluate(h, B, in, controls, out); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t n = (size_t)B, H = (size_t)h->dev.h;
+  // staged through the scratch arrays of bmpc_debug_assemble (synchronous calls on the handle's own stream, like this one)
+  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->contact.ensure(n * H * 2));
+  HIP_TRY(h->phase.ensure(n)); HIP_TRY(h->controls.ensure(n * H * 12));
+  if (in->foot) HIP_TRY(h->foot.ensure(n * 6));
+  if (in->x_cmd) HIP_TRY(h->x_cmd.ensure(n * 12));
+  if (in->mu) HIP_TRY(h->mu.ensure(n * H * 2));
+  if (in->x_ref) HIP_TRY(h->x_ref.ensure(n * H * 12));
+  if (in->foot_ref) HIP_TRY(h->foot_ref.ensure(n * H * 6));
+  const size_t o_c = 0, o_o = o_c + (out->cost ? n : 0), o_v = o_o + (out->objective ? n : 0), o_s = o_v + (out->violation ? n * 4 : 0),
+               tot = o_s + (out->states ? n * H * 13 : 0);
+  HIP_TRY(h->eval_out.ensure(tot));
+  hipStream_t st = h->stream;
+  HIP_TRY(hipMemcpyAsync(h->x_fb.p, in->x_fb, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in->foot) HIP_TRY(hipMemcpyAsync(h->foot.p, in->foot, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->contact.p, in->contact, n * H * 2, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->phase.p, in->phase, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->controls.p, controls, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in->x_cmd) HIP_TRY(hipMemcpyAsync(h->x_cmd.p, in->x_cmd, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in->mu) HIP_TRY(hipMemcpyAsync(h->mu.p, in->mu, n * H * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in->x_ref) HIP_TRY(hipMemcpyAsync(h->x_ref.p, in->x_ref, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in->foot_ref) HIP_TRY(hipMemcpyAsync(h->foot_ref.p, in->foot_ref, n * H * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+  const bmpc_inputs din = {h->x_fb.p, in->foot ? h->foot.p : nullptr, h->contact.p, h->phase.p, in->x_cmd ? h->x_cmd.p : nullptr,
+                           in->mu ? h->mu.p : nullptr, in->x_ref ? h->x_ref.p : nullptr, in->foot_ref ? h->foot_ref.p : nullptr};
+  double* d = h->eval_out.p;
+  const bmpc_eval_out dout = {out->cost ? d + o_c : nullptr, out->objective ? d + o_o : nullptr, out->states ? d + o_s : nullptr,
+                              out->violation ? d + o_v : nullptr};
+  if (int rc = launch_evaluate(h, B, din, h->controls.p, dout, st); rc != BMPC_OK) return rc;
+  if (out->cost) HIP_TRY(hipMemcpyAsync(out->cost, dout.cost, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (out->objective) HIP_TRY(hipMemcpyAsync(out->objective, dout.objective, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (out->violation) HIP_TRY(hipMemcpyAsync(out->violation, dout.violation, n * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (out->states) HIP_TRY(hipMemcpyAsync(out->states, dout.states, n * H * 13 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return BMPC_OK;
 }
 
 static bmpc::LowLevelParams ll_params(const bmpc_params& p) {

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define BMPC_ABI_VERSION 12
+#define BMPC_ABI_VERSION 13
 
 /* `stream` arguments are hipStream_t values passed as void*.  NULL is HIP's null (legacy default)
  * stream -- what torch.cuda.current_stream().cuda_stream is when no stream context is active -- so a
@@ -346,6 +346,49 @@ int bmpc_solve_inputs_device(bmpc_handle h, int B, const bmpc_inputs* in,
                              void* stream);
 int bmpc_debug_assemble_inputs(bmpc_handle h, int B, const bmpc_inputs* in,
                                double* x_ref, double* foot_ref, double* Gt, double* qt);
+
+/*
+ * Evaluation (ABI 13): what the MPC's own model makes of a GIVEN control sequence -- the solver's own (to rank the samples of a
+ * batch by the cost REF:278-286 minimises), or a foreign one (a warm-start guess, a policy's output, last period's plan shifted,
+ * another solver's answer).  Inputs: the descriptor of a solve (references supplied or generated exactly as a solve generates
+ * them) and
+ *   controls [B][h][12] fp32, row k = [f1 f2 m1 m2] (REF:302)
+ * outputs, per instance, each optional (NULL = not wanted; at least one must be given), fp64:
+ *   cost       sum_k (x_{k+1} - x_ref[:, k])' diag(Q) (x_{k+1} - x_ref[:, k]) + u_k' diag(R) u_k over all 13 state entries (the 13th
+ *              contributes 0): non-negative, the number to rank samples by
+ *   objective  the value the reference hands to its solver, 1/2 z'Pz + q'z with z = [X(U); U] (REF:278-297)
+ *              = cost - sum_k sum_i Q_i x_ref[i, k]^2 (i over 13, the row of ones included)
+ *   states     [h][13]: row k = the state after step k, x_{k+1} = A_k x_k + B_k u_k, x_0 = [x_fb; 1], A_k / B_k of REF:148-185
+ *              linearised about x_ref[:, k], foot_ref[:, k]: X(U) of the equality block REF:203-216 -- what `states` of a solve
+ *              is for the solver's own controls (the 13th entry is 1)
+ *   violation  [4]: per row class of Aqp z <= bqp (REF:273-274) the largest positive part of Aqp z - bqp, 0 if the class holds:
+ *              [0] friction pyramid (REF:220-232; per-step mu honoured), [1] force rows of the box (REF:235-251, both signs,
+ *              bounds scaled by `contact`: a swing leg's force counts in full), [2] moment rows of the box, [3] line foot
+ *              (REF:254-271: body axes of R = eul2rotm(x_fb[0:3]), REF:193, whatever x_ref holds; margins 0.01 / 0.02)
+ * Arithmetic: fp64 throughout, on the fp32 inputs widened (the fp64 controls of bmpc_solve_batch_f64 are fp32 values: narrowing them
+ * is exact).  One launch, O(h) work per instance; the result of an instance does not depend on B or on its position in the batch.
+ * A non-finite input, control or reference entry, or a reference pitch within fp32 rounding of +-90 degrees (|cos pitch| < 2^-22:
+ * R_inv of REF:160-164 is singular there), gives NaN in every output of that instance and touches no other instance.
+ *   bmpc_evaluate_device   DEVICE pointers, asynchronous on `stream` (NULL / BMPC_STREAM_OWN as for bmpc_solve_batch_device);
+ *                          nothing is copied
+ *   bmpc_evaluate          HOST pointers, synchronous (staged through the handle's own stream)
+ * A NULL handle, descriptor, `controls` or `out`, all four outputs NULL, foot == NULL without foot_ref, or B outside
+ * [0, max_batch] is BMPC_ERR_INVALID; the NULL checks come before a device is touched.  Every supported horizon (1 .. 40), and the
+ * same kernel whatever family the handle solves with (`path` plays no part).  The evaluation reads the handle's parameter block
+ * (bmpc_set_params takes effect; the solver's own knobs are not used) and none of its per-solve state: the warm-start buffer, the
+ * dispatch order, the event pair and the I/O block are left alone, and bmpc_last_kernel_ms keeps reporting the last SOLVE.  Queued
+ * behind a bmpc_solve_*_device call on the same stream with that call's `controls` buffer as input, it needs no synchronisation
+ * in between.
+ */
+typedef struct bmpc_eval_out {
+  double* cost;        /* [B] or NULL */
+  double* objective;   /* [B] or NULL */
+  double* states;      /* [B][h][13] or NULL */
+  double* violation;   /* [B][4] or NULL: friction, force box, moment box, line foot */
+} bmpc_eval_out;
+int bmpc_evaluate_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls,
+                         const bmpc_eval_out* out, void* stream);
+int bmpc_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out);
 
 /*
  * The step either side of the MPC solve, batched; HOST pointers, synchronous.
