@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "bmpc.h"
+#include "bmpc_model.hip"
 
 namespace bmpc {
 
@@ -260,12 +261,11 @@ evaluate_kernel(const EvalParams P, const int B,
   double viol[4] = {0.0, 0.0, 0.0, 0.0};
   {
     // body axes of the line-foot rows: columns y and z of R = eul2rotm(x_fb[0:3]) = Rz(e2) Ry(e1) Rx(e0)  (REF:124-138, 193, 259-262)
-    double s0, c0, s1, c1, s2, c2;
+    double s0, c0, s1, c1, s2, c2, ey[3], ez[3];
     sincos(xfb[0], &s0, &c0);
     sincos(xfb[1], &s1, &c1);
     sincos(xfb[2], &s2, &c2);
-    const double ey[3] = {c2 * s1 * s0 - s2 * c0, s2 * s1 * s0 + c2 * c0, c1 * s0};
-    const double ez[3] = {c2 * s1 * c0 + s2 * s0, s2 * s1 * c0 - c2 * s0, c1 * c0};
+    body_axes(s0, c0, s1, c1, s2, c2, ey, ez);
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       const double* f = &u[3 * g];

@@ -36,10 +36,11 @@
 #endif
 #include <stdint.h>
 
+#include "bmpc_model.hip"
+
 namespace bmpc {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
-typedef double RT;                       // iterate / residual / block-algebra arithmetic
 
 #ifndef BMPC_EMU
 __device__ __forceinline__ double rcp_approx(double x) { return __builtin_amdgcn_rcp(x); }
@@ -486,25 +487,6 @@ __device__ __forceinline__ void cross3(const T* a, const T* b, T* o) {
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// General (non-box) rows of one foot block over v = [f(3), m(3)]:
-// rows 0..3 friction (+x, +y, -x, -y; REF:220-229), rows 4, 5 line foot (REF:259-262).
-__device__ __forceinline__ void general_rows(float mu, const float* ey, const float* ez, float lh,
-                                             float lt, float (&G)[6][6]) {
-#pragma unroll
-  for (int r = 0; r < 6; ++r)
-#pragma unroll
-    for (int b = 0; b < 6; ++b) G[r][b] = 0.f;
-  G[0][0] = 1.f;  G[0][2] = -mu;
-  G[1][1] = 1.f;  G[1][2] = -mu;
-  G[2][0] = -1.f; G[2][2] = -mu;
-  G[3][1] = -1.f; G[3][2] = -mu;
-#pragma unroll
-  for (int b = 0; b < 3; ++b) {
-    G[4][b] = -lh * ez[b];  G[4][3 + b] = ey[b];
-    G[5][b] = -lt * ez[b];  G[5][3 + b] = -ey[b];
-  }
-}
-
 // The solve, as the body of two kernels: solve_kernel<H> (PROF = false: no trace of the diagnostics in the code) and
 // solve_kernel_prof<H> (in-kernel cycle stamps for tools/phase_cycles.py, launched while a profile buffer is set).
 template <int H, bool PROF>
@@ -863,8 +845,10 @@ solve_body(const DevParams& P, const int B,
       // and foot of the instance and lives in LDS (plus its transpose); a lane keeps only the mu term it needs.  Formed here by
       // one lane of the LAST wave, which has the fewest tiles below and would wait for the others at the barrier.
       const RT s0 = sm.Gu[0][0], c0 = sm.Gu[0][1], s1 = sm.Gu[0][2], c1 = sm.Gu[0][3], s2 = sm.Gu[0][4], c2 = sm.Gu[0][5];
-      const float ey[3] = {(float)(c2 * s1 * s0 - s2 * c0), (float)(s2 * s1 * s0 + c2 * c0), (float)(c1 * s0)};
-      const float ez[3] = {(float)(c2 * s1 * c0 + s2 * s0), (float)(s2 * s1 * c0 - c2 * s0), (float)(c1 * c0)};
+      RT eyd[3], ezd[3];
+      body_axes(s0, c0, s1, c1, s2, c2, eyd, ezd);
+      const float ey[3] = {(float)eyd[0], (float)eyd[1], (float)eyd[2]};
+      const float ez[3] = {(float)ezd[0], (float)ezd[1], (float)ezd[2]};
 #pragma unroll
       for (int a = 0; a < 3; ++a) { sm.eyz[a] = ey[a]; sm.eyz[3 + a] = ez[a]; }
       float G[6][6];
@@ -1824,27 +1808,20 @@ solve_body(const DevParams& P, const int B,
         const RT xto = xo - (RT)s;
         const RT ztg = axg - (RT)sg;
         const RT ztb = xto;
-        // box row
+        // box row, then the general row (l = -inf, u = 0)
         {
-          const RT zr = alpha * ztb + (1 - alpha) * zb;
-          const RT cand = zr + yb * irvb;
-          const RT zn = fmin(fmax(cand, widen(lb)), widen(ub));
-          d_yb = widen(rvb) * (zr - zn);
+          RT zn;
+          project_box(alpha, ztb, zb, yb, irvb, widen(lb), widen(ub), widen(rvb), zn, d_yb, st_pb);
           yb += d_yb;
           d_zb = zn - zb;
           zb = zn;
-          st_pb = ztb - zn;
         }
-        // general row: l = -inf, u = 0
         {
-          const RT zr = alpha * ztg + (1 - alpha) * zg;
-          const RT cand = zr + yg * irvg;
-          const RT zn = fmin(cand, (RT)0);
-          d_yg = widen(rvg) * (zr - zn);
+          RT zn;
+          project_general(alpha, ztg, zg, yg, irvg, widen(rvg), zn, d_yg, st_pg);
           yg += d_yg;
           d_zg = zn - zg;
           zg = zn;
-          st_pg = ztg - zn;
         }
         st_x = xto; st_g = ztg; st_dx = xto - xo;
         d_ax = alpha * (ztg - axg);

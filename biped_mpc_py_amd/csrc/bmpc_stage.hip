@@ -41,6 +41,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "bmpc_model.hip"
+
 namespace bmpc {
 
 #ifndef BMPC_EMU
@@ -459,12 +461,13 @@ stage_body(const DevParams& P, const int B,
   {
     float ey[3], ez[3];                        // columns 1, 2 of R = eul2rotm(x_fb[0:3])  (REF:124-138, 193)
     {
-      RT sr, cr, sp, cp, sy, cy;
+      RT sr, cr, sp, cp, sy, cy, eyd[3], ezd[3];
       sincos(xfb[0], &sr, &cr);
       sincos(xfb[1], &sp, &cp);
       sincos(xfb[2], &sy, &cy);
-      ey[0] = (float)(cy * sp * sr - sy * cr); ey[1] = (float)(sy * sp * sr + cy * cr); ey[2] = (float)(cp * sr);
-      ez[0] = (float)(cy * sp * cr + sy * sr); ez[1] = (float)(sy * sp * cr - cy * sr); ez[2] = (float)(cp * cr);
+      body_axes(sr, cr, sp, cp, sy, cy, eyd, ezd);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) { ey[a] = (float)eyd[a]; ez[a] = (float)ezd[a]; }
     }
     if (lt == 0) {
 #pragma unroll
@@ -1488,21 +1491,11 @@ stage_body(const DevParams& P, const int B,
       const RT xto = xo[s] - (RT)dd.x;
       const RT ztg = axg[s] - (RT)dd.y;
       const RT ztb = xto;
-      RT st_pb, st_pg, znb, zng, ybn, ygn;
-      {
-        const RT zr = alpha * ztb + (1 - alpha) * zb[s];
-        const RT cand = zr + yb[s] * irvb[s];
-        znb = fmin(fmax(cand, widen(lb[s])), widen(ub[s]));
-        ybn = yb[s] + widen(rvb[s]) * (zr - znb);
-        st_pb = ztb - znb;
-      }
-      {
-        const RT zr = alpha * ztg + (1 - alpha) * zg[s];
-        const RT cand = zr + yg[s] * irvg[s];
-        zng = fmin(cand, (RT)0);
-        ygn = yg[s] + widen(rvg[s]) * (zr - zng);
-        st_pg = ztg - zng;
-      }
+      RT st_pb, st_pg, znb, zng, ybn, ygn, dy;
+      project_box(alpha, ztb, zb[s], yb[s], irvb[s], widen(lb[s]), widen(ub[s]), widen(rvb[s]), znb, dy, st_pb);
+      ybn = yb[s] + dy;
+      project_general(alpha, ztg, zg[s], yg[s], irvg[s], widen(rvg[s]), zng, dy, st_pg);
+      ygn = yg[s] + dy;
       if constexpr (MODE != 2) {
         if (check_now && sreal[s]) {
           rp = fmaxf(rp, fmaxf(fabsf((float)st_pb), fabsf((float)st_pg)));

@@ -66,6 +66,19 @@ CONFIGS = {
 }
 
 
+# The kernel sources, in csrc/: everything that is compiled into libbmpc.so and into the emulation libraries of tests/emu.  THE list:
+# the build, the source hash below and the emulation drivers read it (kernel_source_paths), so that an edit of any of these files
+# rebuilds all of them.  bmpc_capi.hip, the first, is the translation unit that includes the others.
+KERNEL_SOURCES = ("bmpc_capi.hip", "bmpc_kernels.hip", "bmpc_stage.hip", "bmpc_lowlevel.hip", "bmpc_evaluate.hip", "bmpc_model.hip")
+
+
+def kernel_source_paths():
+    """Absolute paths of KERNEL_SOURCES, then of the C ABI header include/bmpc.h."""
+    import os
+    pkg = os.path.dirname(os.path.abspath(__file__))
+    return [os.path.join(pkg, "csrc", n) for n in KERNEL_SOURCES] + [os.path.join(os.path.dirname(pkg), "include", "bmpc.h")]
+
+
 def kernel_source_hash():
     """sha256 (first 16 hex digits) over the CODE of the kernel sources -- comments and white space stripped, so that
     editing the commentary does not orphan a measurement: stamps measurements that are replayed later
@@ -73,10 +86,8 @@ def kernel_source_hash():
     import hashlib
     import os
     import re
-    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     hsh = hashlib.sha256()
-    # everything that decides the code object and the parameter block it runs with: the four sources, the C ABI header
+    # everything that decides the code object and the parameter block it runs with: the sources, the C ABI header
     # (DevParams / bmpc_params layout, defaults) and the compile flags of __graft_entry__.build()
     try:
         import __graft_entry__ as _ge
@@ -84,8 +95,7 @@ def kernel_source_hash():
     except Exception:                       # (package used outside the repository: the sources alone)
         flags = ""
     hsh.update(flags.encode())
-    for path in [os.path.join(here, n) for n in ("bmpc_kernels.hip", "bmpc_stage.hip", "bmpc_capi.hip", "bmpc_lowlevel.hip")] + \
-                [os.path.join(root, "include", "bmpc.h")]:
+    for path in kernel_source_paths():
         if not os.path.exists(path):
             continue
         with open(path, "r", encoding="utf-8") as fh:

@@ -14,8 +14,8 @@ CLANG = os.environ.get("BMPC_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
 
 
 def build(force=False):
-    srcs = [os.path.join(HERE, "bmpc_emu.cpp"), os.path.join(ROOT, "biped_mpc_py_amd", "csrc", "bmpc_kernels.hip"),
-            os.path.join(ROOT, "biped_mpc_py_amd", "csrc", "bmpc_stage.hip"), os.path.join(ROOT, "include", "bmpc.h")]
+    from biped_mpc_py_amd.synth import kernel_source_paths
+    srcs = [os.path.join(HERE, "bmpc_emu.cpp")] + kernel_source_paths()
     if force or not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in srcs):
         subprocess.check_call([CLANG, "-std=c++20", "-O1", "-pthread", "-fPIC", "-shared", "-D_GNU_SOURCE",
                                "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-x", "c++", srcs[0], "-o", SO])

@@ -12,9 +12,8 @@ SO = os.path.join(emu.HERE, "libbmpc_emu_refs.so")
 
 
 def build(force=False):
-    srcs = [os.path.join(emu.HERE, "bmpc_emu_refs.cpp"), os.path.join(emu.HERE, "bmpc_emu.cpp"),
-            os.path.join(emu.ROOT, "biped_mpc_py_amd", "csrc", "bmpc_kernels.hip"),
-            os.path.join(emu.ROOT, "biped_mpc_py_amd", "csrc", "bmpc_stage.hip"), os.path.join(emu.ROOT, "include", "bmpc.h")]
+    from biped_mpc_py_amd.synth import kernel_source_paths
+    srcs = [os.path.join(emu.HERE, "bmpc_emu_refs.cpp"), os.path.join(emu.HERE, "bmpc_emu.cpp")] + kernel_source_paths()
     if force or not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in srcs):
         subprocess.check_call([emu.CLANG, "-std=c++20", "-O1", "-pthread", "-fPIC", "-shared", "-D_GNU_SOURCE",
                                "-ffp-contract=off", "-I" + os.path.join(emu.ROOT, "include"), "-I" + emu.HERE, "-x", "c++", srcs[0],

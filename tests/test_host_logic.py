@@ -203,10 +203,10 @@ def test_kernel_source_hash_covers_code_not_commentary():
     """synth.kernel_source_hash strips comments before hashing; that is only sound while no string literal of the kernel
     sources contains a comment opener."""
     import re
-    from biped_mpc_py_amd.synth import kernel_source_hash
-    here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "biped_mpc_py_amd", "csrc")
-    for name in ("bmpc_kernels.hip", "bmpc_stage.hip", "bmpc_capi.hip", "bmpc_lowlevel.hip", os.path.join("..", "..", "include", "bmpc.h")):
-        text = open(os.path.join(here, name), encoding="utf-8").read()
+    from biped_mpc_py_amd.synth import kernel_source_hash, kernel_source_paths
+    assert any(n.endswith("bmpc_evaluate.hip") for n in kernel_source_paths())
+    for name in kernel_source_paths():
+        text = open(name, encoding="utf-8").read()
         for m in re.finditer(r'"([^"\n]*)"', text):
             assert "//" not in m.group(1) and "/*" not in m.group(1), (name, m.group(0))
     assert re.fullmatch(r"[0-9a-f]{16}", kernel_source_hash())
