@@ -8,7 +8,8 @@ from .params import MPC, Biped, pack_params                                  # n
 from .api import (BatchSolver, solve_mpc, solve_mpc_batch, get_contact_sequence,   # noqa: F401
                   phase_index, phase_indices, lowLevelControl, getFootPositionWorld, SolverStatusWarning,
                   close_cached_solvers, get_reference_trajectory, get_reference_foot_trajectory,
-                  reference_trajectories_batch, references_to_kernel_layout, evaluate_mpc, evaluate_mpc_batch)
+                  reference_trajectories_batch, references_to_kernel_layout, evaluate_mpc, evaluate_mpc_batch,
+                  evaluate_grad_mpc, evaluate_grad_mpc_batch)
 from . import sharding                                                        # noqa: F401
 from ._lib import BmpcError                                                   # noqa: F401
 
@@ -16,4 +17,5 @@ __all__ = ["MPC", "Biped", "pack_params", "BatchSolver", "solve_mpc", "solve_mpc
            "get_contact_sequence", "phase_index", "phase_indices", "lowLevelControl", "getFootPositionWorld", "sharding",
            "BmpcError", "SolverStatusWarning", "close_cached_solvers",
            "get_reference_trajectory", "get_reference_foot_trajectory", "reference_trajectories_batch",
-           "references_to_kernel_layout", "evaluate_mpc", "evaluate_mpc_batch"]
+           "references_to_kernel_layout", "evaluate_mpc", "evaluate_mpc_batch",
+           "evaluate_grad_mpc", "evaluate_grad_mpc_batch"]

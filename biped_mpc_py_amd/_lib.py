@@ -20,7 +20,7 @@ EXPORTS = (
     "bmpc_host_io", "bmpc_solve_batch_io", "bmpc_host_io_generation",
     "bmpc_debug_assemble", "bmpc_debug_set_profile", "bmpc_last_kernel_ms",
     "bmpc_solve_inputs_f64", "bmpc_solve_inputs_device", "bmpc_debug_assemble_inputs",
-    "bmpc_evaluate_device", "bmpc_evaluate",
+    "bmpc_evaluate_device", "bmpc_evaluate", "bmpc_evaluate_grad_device", "bmpc_evaluate_grad",
     "bmpc_foot_position_world", "bmpc_foot_position_world_device",
     "bmpc_low_level_control", "bmpc_low_level_control_device",
     "bmpc_gait_default", "bmpc_contact_sequence", "bmpc_contact_sequence_device",
@@ -47,6 +47,11 @@ class CInputs(C.Structure):
 class CEvalOut(C.Structure):
     """`bmpc_eval_out` of include/bmpc.h: the outputs of an evaluation, each optional (NULL: not wanted)."""
     _fields_ = [(n, C.c_void_p) for n in ("cost", "objective", "states", "violation")]
+
+
+class CGradOut(C.Structure):
+    """`bmpc_grad_out` of include/bmpc.h: the outputs of a cost gradient, each optional (NULL: not wanted)."""
+    _fields_ = [(n, C.c_void_p) for n in ("cost", "grad_u", "grad_x0")]
 
 
 class BmpcError(RuntimeError):
@@ -140,6 +145,8 @@ def load():
     lib.bmpc_debug_assemble_inputs.argtypes = [vp, ip, C.POINTER(CInputs)] + [vp] * 4
     lib.bmpc_evaluate_device.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CEvalOut), vp]
     lib.bmpc_evaluate.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CEvalOut)]
+    lib.bmpc_evaluate_grad_device.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CGradOut), vp]
+    lib.bmpc_evaluate_grad.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CGradOut)]
     lib.bmpc_foot_position_world.argtypes = [vp, ip, vp, vp, vp]
     lib.bmpc_foot_position_world_device.argtypes = [vp, ip, vp, vp, vp, vp]
     lib.bmpc_low_level_control.argtypes = [vp, ip] + [vp] * 8

@@ -146,6 +146,36 @@ class _HandleOwner:
             pass
 
 
+_COST_FUNCTION = None
+
+
+def _cost_function():
+    """The `torch.autograd.Function` behind `BatchSolver.cost_torch`, built on first use (the package imports without torch)."""
+    global _COST_FUNCTION
+    if _COST_FUNCTION is not None:
+        return _COST_FUNCTION.apply
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _Cost(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, solver, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref):
+            r = solver.evaluate_grad_device(x_fb, foot, contact, phase, controls, x_cmd=x_cmd, mu=mu, x_ref=x_ref, foot_ref=foot_ref)
+            ctx.save_for_backward(r["grad_u"], r["grad_x0"])
+            return r["cost"]
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_output):
+            grad_u, grad_x0 = ctx.saved_tensors
+            g_x = (grad_output[:, None] * grad_x0).to(torch.float32) if ctx.needs_input_grad[1] else None
+            g_u = (grad_output[:, None, None] * grad_u).to(torch.float32) if ctx.needs_input_grad[5] else None
+            return None, g_x, None, None, None, g_u, None, None, None, None
+
+    _COST_FUNCTION = _Cost
+    return _Cost.apply
+
+
 class BatchSolver:
     """Owns one `bmpc_handle` (device memory + stream) for a fixed parameter block."""
 
@@ -262,6 +292,26 @@ class BatchSolver:
         inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
         eo = _lib.CEvalOut(_ptr(res["cost"]), _ptr(res["objective"]), _ptr(res["states"]), _ptr(res["violation"]))
         _lib.check(self._lib.bmpc_evaluate(self._h, B, C.byref(inp), _ptr(c32), C.byref(eo)))
+        return res
+
+    def evaluate_grad(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None):
+        """Gradient of `evaluate`'s cost (`bmpc_evaluate_grad`, include/bmpc.h): arguments as `evaluate` takes them.  Returns
+        dict(cost (B,), grad_u (B,h,12), grad_x0 (B,12)), NumPy fp64: `cost` with the bits `evaluate` gives, d cost / d controls, and
+        d cost / d x_fb through the initial condition only -- the references, lever arms and linearisation are held fixed whether
+        they were supplied or generated (generated references depend on x_fb; that dependence is not differentiated).  The cost is
+        an exact quadratic in the controls: `grad_u` at U + D minus `grad_u` at U is the Hessian times D.  Bad instances as in
+        `evaluate`: NaN in all their outputs."""
+        c32 = _controls_f32(controls, self.h)
+        B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
+        if c32.shape[0] != B:
+            raise ValueError(f"controls must have shape ({B}, {self.h}, 12), got {c32.shape}")
+        x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h, finite=False)
+        if foot is None and foot_ref is None:
+            raise ValueError("foot is required unless foot_ref is given")
+        res = dict(cost=np.empty(B, np.float64), grad_u=np.empty((B, self.h, 12), np.float64), grad_x0=np.empty((B, 12), np.float64))
+        inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
+        go = _lib.CGradOut(_ptr(res["cost"]), _ptr(res["grad_u"]), _ptr(res["grad_x0"]))
+        _lib.check(self._lib.bmpc_evaluate_grad(self._h, B, C.byref(inp), _ptr(c32), C.byref(go)))
         return res
 
     def _io_views(self, B, with_x_cmd, with_mu, with_states):
@@ -434,6 +484,50 @@ class BatchSolver:
                            chk(states, torch.float64, (B, h, 13)), chk(violation, torch.float64, (B, 4)))
         _lib.check(self._lib.bmpc_evaluate_device(self._h, B, C.byref(inp), chk(controls, torch.float32, (B, h, 12)), C.byref(eo), st))
         return dict(cost=cost, objective=objective, violation=violation, states=states)
+
+    def evaluate_grad_device(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None,
+                             cost=None, grad_u=None, grad_x0=None, stream=None):
+        """`evaluate_grad` on CUDA(HIP) torch tensors of this solver's device (`bmpc_evaluate_grad_device`): inputs as
+        `evaluate_device` takes them.  Outputs are float64 tensors cost (B,), grad_u (B,h,12), grad_x0 (B,12), allocated where not
+        passed.  Asynchronous on `stream` (default: torch's current stream); nothing crosses PCIe.  Returns dict(cost, grad_u,
+        grad_x0)."""
+        import torch
+        B = x_fb.shape[0]
+        h = self.h
+        dev = x_fb.device
+
+        def chk(t, dtype, shape):
+            if t is None:
+                return None
+            if t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"expected contiguous {dtype} tensor of shape {shape} on {dev}")
+            return t.data_ptr()
+
+        if dev.type != "cuda" or dev.index != self.device:
+            raise ValueError(f"tensors must live on cuda:{self.device}")
+        f64 = lambda shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        cost = f64((B,)) if cost is None else cost
+        grad_u = f64((B, h, 12)) if grad_u is None else grad_u
+        grad_x0 = f64((B, 12)) if grad_x0 is None else grad_x0
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        inp = _lib.CInputs(chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)),
+                           chk(contact, torch.uint8, (B, h, 2)), chk(phase, torch.int32, (B,)),
+                           chk(x_cmd, torch.float32, (B, 12)), chk(mu, torch.float32, (B, h, 2)),
+                           chk(x_ref, torch.float32, (B, h, 12)), chk(foot_ref, torch.float32, (B, h, 6)))
+        go = _lib.CGradOut(chk(cost, torch.float64, (B,)), chk(grad_u, torch.float64, (B, h, 12)), chk(grad_x0, torch.float64, (B, 12)))
+        _lib.check(self._lib.bmpc_evaluate_grad_device(self._h, B, C.byref(inp), chk(controls, torch.float32, (B, h, 12)), C.byref(go), st))
+        return dict(cost=cost, grad_u=grad_u, grad_x0=grad_x0)
+
+    def cost_torch(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None):
+        """`evaluate`'s cost as a differentiable torch value: float64 tensor (B,) on the device, with gradients to `controls` (B,h,12)
+        and `x_fb` (B,12), both float32 CUDA tensors; every other argument is non-differentiable.  The forward is ONE
+        `bmpc_evaluate_grad_device` launch on torch's current stream, which also leaves `grad_u` / `grad_x0` behind; the backward
+        scales them by the incoming gradient per instance and casts to float32 -- no second launch, no synchronisation, no second
+        derivative (`once_differentiable`).
+        `x_fb.grad` follows the fixed-references convention of `evaluate_grad`: it is d cost / d x_fb through the initial condition
+        only, with the references, lever arms and linearisation held fixed whether they were supplied or generated.  With supplied
+        references that is the full derivative; generated references move with x_fb, and that dependence is not differentiated."""
+        return _cost_function()(self, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref)
 
     # ---- the step either side of the solve (SURVEY 8(f) row 1) ------------------------------------
     def foot_position_world(self, x_fb, q):
@@ -683,6 +777,37 @@ def evaluate_mpc(x_fb, t, foot, mpc, biped, contact, controls, half=None, device
                            x_ref=None if x_ref is None else np.asarray(x_ref)[None],
                            foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None])
     return dict(cost=float(r["cost"][0]), objective=float(r["objective"][0]), violation=r["violation"][0], states=r["states"][0])
+
+
+def evaluate_grad_mpc_batch(x_fb, t, foot, contact, controls, mpc=None, biped=None, x_cmd=None, mu=None, phase=None, half=None,
+                            device=0, x_ref=None, foot_ref=None):
+    """Gradient of the cost `evaluate_mpc_batch` returns: the same call surface (references in the reference's orientation, the
+    cached handle per horizon and device).  Returns dict(cost (B,), grad_u (B,h,12), grad_x0 (B,12)) as `BatchSolver.evaluate_grad`."""
+    from .params import MPC
+    mpc = mpc if mpc is not None else MPC()
+    c32 = _controls_f32(controls, int(mpc.h))
+    xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
+    solver = _cached_solver(mpc, biped, half, device, None)
+    if phase is None:
+        phase = phase_indices(t, mpc.dt, mpc.h)
+    return solver.evaluate_grad(x_fb, foot, contact, phase, c32, x_cmd=x_cmd, mu=mu, x_ref=xr, foot_ref=fr)
+
+
+def evaluate_grad_mpc(x_fb, t, foot, mpc, biped, contact, controls, half=None, device=0, x_ref=None, foot_ref=None):
+    """`evaluate_grad_mpc_batch` for one instance with `evaluate_mpc`'s arguments.  Returns dict(cost float, grad_u (h,12),
+    grad_x0 (12,))."""
+    h = int(mpc.h)
+    c = np.asarray(controls)
+    if c.shape != (h, 12):
+        raise ValueError(f"controls must have shape ({h}, 12), got {c.shape}")
+    contact = np.asarray(contact)
+    if contact.ndim != 2 or contact.shape[1] != 2 or contact.shape[0] < h:
+        raise ValueError(f"contact must have at least {h} rows of 2 (REF:239-249 indexes contact[k] for k < h)")
+    r = evaluate_grad_mpc_batch(np.asarray(x_fb, float).reshape(1, 12), [t], np.asarray(foot, float).reshape(1, 6),
+                                contact[None, :h, :], c[None], mpc=mpc, biped=biped, half=half, device=device,
+                                x_ref=None if x_ref is None else np.asarray(x_ref)[None],
+                                foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None])
+    return dict(cost=float(r["cost"][0]), grad_u=r["grad_u"][0], grad_x0=r["grad_x0"][0])
 
 
 def reference_trajectories_batch(x_fb, t, foot, contact, mpc=None, biped=None, x_cmd=None, phase=None, half=None, device=0):

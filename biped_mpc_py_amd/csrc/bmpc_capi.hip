@@ -5,6 +5,7 @@
 #include "bmpc_stage.hip"
 #include "bmpc_lowlevel.hip"
 #include "bmpc_evaluate.hip"
+#include "bmpc_evaluate_grad.hip"
 
 #include <chrono>
 #include <cmath>
@@ -1046,26 +1047,77 @@ int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* fo
 
 // ---- evaluation of given controls (bmpc_evaluate.hip): one launch, nothing of the handle's per-solve state involved
 
-// what both entries check before a device is touched: an error code (< 0), BMPC_OK when there is nothing to do, 1 to go on
-static int check_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out) {
+// what every entry checks before a device is touched: an error code (< 0), BMPC_OK when there is nothing to do, 1 to go on.
+// `out`: the entry's output descriptor, `any_out`: whether one of its members is non-null, `null_out` / `none_out`: the messages
+static int check_evaluate_args(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const void* out, bool any_out,
+                               const char* null_out, const char* none_out) {
   if (!h) return fail(BMPC_ERR_INVALID, "null handle");
   if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
   if (!controls) return fail(BMPC_ERR_INVALID, "null controls");
-  if (!out) return fail(BMPC_ERR_INVALID, "null bmpc_eval_out");
-  if (!out->cost && !out->objective && !out->states && !out->violation)
-    return fail(BMPC_ERR_INVALID, "bmpc_eval_out: at least one of cost, objective, states, violation must be non-null");
+  if (!out) return fail(BMPC_ERR_INVALID, null_out);
+  if (!any_out) return fail(BMPC_ERR_INVALID, none_out);
   return check_common(h, B, in->x_fb, in->foot, in->contact, in->phase, controls, in->foot_ref);
 }
 
-static int launch_evaluate(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const bmpc_eval_out& out, hipStream_t st) {
+static int check_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out) {
+  return check_evaluate_args(h, B, in, controls, out, out && (out->cost || out->objective || out->states || out->violation),
+                             "null bmpc_eval_out", "bmpc_eval_out: at least one of cost, objective, states, violation must be non-null");
+}
+
+static int check_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_grad_out* out) {
+  return check_evaluate_args(h, B, in, controls, out, out && (out->cost || out->grad_u || out->grad_x0),
+                             "null bmpc_grad_out", "bmpc_grad_out: at least one of cost, grad_u, grad_x0 must be non-null");
+}
+
+static dim3 evaluate_grid(bmpc_handle h, int B) {
   const int hh = h->params.h;
   const int L = hh <= 16 ? 16 : (hh <= 32 ? 32 : 64);          // lanes per instance (bmpc_evaluate.hip)
   const long long lanes = (long long)B * L;
+  return dim3((unsigned)((lanes + bmpc::EVAL_NT - 1) / bmpc::EVAL_NT));
+}
+
+static int launch_evaluate(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const bmpc_eval_out& out, hipStream_t st) {
   const bmpc::EvalOut o = {out.cost, out.objective, out.states, out.violation};
-  hipLaunchKernelGGL(bmpc::evaluate_kernel, dim3((unsigned)((lanes + bmpc::EVAL_NT - 1) / bmpc::EVAL_NT)), dim3(bmpc::EVAL_NT), 0, st,
+  hipLaunchKernelGGL(bmpc::evaluate_kernel, evaluate_grid(h, B), dim3(bmpc::EVAL_NT), 0, st,
                      bmpc::eval_params(h->params, h->dev.Iinv), B, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd, in.mu, in.x_ref,
                      in.foot_ref, controls, o);
   HIP_TRY(hipGetLastError());
+  return BMPC_OK;
+}
+
+static int launch_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const bmpc_grad_out& out,
+                                hipStream_t st) {
+  const bmpc::GradOut o = {out.cost, out.grad_u, out.grad_x0};
+  hipLaunchKernelGGL(bmpc::evaluate_grad_kernel, evaluate_grid(h, B), dim3(bmpc::EVAL_NT), 0, st,
+                     bmpc::eval_params(h->params, h->dev.Iinv), B, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd, in.mu, in.x_ref,
+                     in.foot_ref, controls, o);
+  HIP_TRY(hipGetLastError());
+  return BMPC_OK;
+}
+
+// host inputs of an evaluation onto the device, queued on the handle's own stream: staged through the scratch arrays of
+// bmpc_debug_assemble (synchronous calls on that stream, like the host entries here).  `din`: the descriptor of the copies
+static int stage_evaluate_inputs(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, bmpc_inputs* din) {
+  const size_t n = (size_t)B, H = (size_t)h->dev.h;
+  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->contact.ensure(n * H * 2));
+  HIP_TRY(h->phase.ensure(n)); HIP_TRY(h->controls.ensure(n * H * 12));
+  if (in->foot) HIP_TRY(h->foot.ensure(n * 6));
+  if (in->x_cmd) HIP_TRY(h->x_cmd.ensure(n * 12));
+  if (in->mu) HIP_TRY(h->mu.ensure(n * H * 2));
+  if (in->x_ref) HIP_TRY(h->x_ref.ensure(n * H * 12));
+  if (in->foot_ref) HIP_TRY(h->foot_ref.ensure(n * H * 6));
+  hipStream_t st = h->stream;
+  HIP_TRY(hipMemcpyAsync(h->x_fb.p, in->x_fb, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in->foot) HIP_TRY(hipMemcpyAsync(h->foot.p, in->foot, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->contact.p, in->contact, n * H * 2, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->phase.p, in->phase, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->controls.p, controls, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in->x_cmd) HIP_TRY(hipMemcpyAsync(h->x_cmd.p, in->x_cmd, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in->mu) HIP_TRY(hipMemcpyAsync(h->mu.p, in->mu, n * H * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in->x_ref) HIP_TRY(hipMemcpyAsync(h->x_ref.p, in->x_ref, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in->foot_ref) HIP_TRY(hipMemcpyAsync(h->foot_ref.p, in->foot_ref, n * H * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+  *din = {h->x_fb.p, in->foot ? h->foot.p : nullptr, h->contact.p, h->phase.p, in->x_cmd ? h->x_cmd.p : nullptr,
+          in->mu ? h->mu.p : nullptr, in->x_ref ? h->x_ref.p : nullptr, in->foot_ref ? h->foot_ref.p : nullptr};
   return BMPC_OK;
 }
 
@@ -1079,29 +1131,12 @@ int bmpc_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* cont
   if (int rc = check_evaluate(h, B, in, controls, out); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B, H = (size_t)h->dev.h;
-  // staged through the scratch arrays of bmpc_debug_assemble (synchronous calls on the handle's own stream, like this one)
-  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->contact.ensure(n * H * 2));
-  HIP_TRY(h->phase.ensure(n)); HIP_TRY(h->controls.ensure(n * H * 12));
-  if (in->foot) HIP_TRY(h->foot.ensure(n * 6));
-  if (in->x_cmd) HIP_TRY(h->x_cmd.ensure(n * 12));
-  if (in->mu) HIP_TRY(h->mu.ensure(n * H * 2));
-  if (in->x_ref) HIP_TRY(h->x_ref.ensure(n * H * 12));
-  if (in->foot_ref) HIP_TRY(h->foot_ref.ensure(n * H * 6));
   const size_t o_c = 0, o_o = o_c + (out->cost ? n : 0), o_v = o_o + (out->objective ? n : 0), o_s = o_v + (out->violation ? n * 4 : 0),
                tot = o_s + (out->states ? n * H * 13 : 0);
   HIP_TRY(h->eval_out.ensure(tot));
+  bmpc_inputs din;
+  if (int rc = stage_evaluate_inputs(h, B, in, controls, &din); rc != BMPC_OK) return rc;
   hipStream_t st = h->stream;
-  HIP_TRY(hipMemcpyAsync(h->x_fb.p, in->x_fb, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in->foot) HIP_TRY(hipMemcpyAsync(h->foot.p, in->foot, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->contact.p, in->contact, n * H * 2, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->phase.p, in->phase, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->controls.p, controls, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in->x_cmd) HIP_TRY(hipMemcpyAsync(h->x_cmd.p, in->x_cmd, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in->mu) HIP_TRY(hipMemcpyAsync(h->mu.p, in->mu, n * H * 2 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in->x_ref) HIP_TRY(hipMemcpyAsync(h->x_ref.p, in->x_ref, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in->foot_ref) HIP_TRY(hipMemcpyAsync(h->foot_ref.p, in->foot_ref, n * H * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-  const bmpc_inputs din = {h->x_fb.p, in->foot ? h->foot.p : nullptr, h->contact.p, h->phase.p, in->x_cmd ? h->x_cmd.p : nullptr,
-                           in->mu ? h->mu.p : nullptr, in->x_ref ? h->x_ref.p : nullptr, in->foot_ref ? h->foot_ref.p : nullptr};
   double* d = h->eval_out.p;
   const bmpc_eval_out dout = {out->cost ? d + o_c : nullptr, out->objective ? d + o_o : nullptr, out->states ? d + o_s : nullptr,
                               out->violation ? d + o_v : nullptr};
@@ -1110,6 +1145,33 @@ int bmpc_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* cont
   if (out->objective) HIP_TRY(hipMemcpyAsync(out->objective, dout.objective, n * sizeof(double), hipMemcpyDeviceToHost, st));
   if (out->violation) HIP_TRY(hipMemcpyAsync(out->violation, dout.violation, n * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
   if (out->states) HIP_TRY(hipMemcpyAsync(out->states, dout.states, n * H * 13 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return BMPC_OK;
+}
+
+// ---- gradient of the evaluated cost (bmpc_evaluate_grad.hip): the entries of the evaluation with other outputs
+
+int bmpc_evaluate_grad_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_grad_out* out, void* stream) {
+  if (int rc = check_evaluate_grad(h, B, in, controls, out); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return launch_evaluate_grad(h, B, *in, controls, *out, pick_stream(h, stream));
+}
+
+int bmpc_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_grad_out* out) {
+  if (int rc = check_evaluate_grad(h, B, in, controls, out); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t n = (size_t)B, H = (size_t)h->dev.h;
+  const size_t o_c = 0, o_x = o_c + (out->cost ? n : 0), o_u = o_x + (out->grad_x0 ? n * 12 : 0), tot = o_u + (out->grad_u ? n * H * 12 : 0);
+  HIP_TRY(h->eval_out.ensure(tot));
+  bmpc_inputs din;
+  if (int rc = stage_evaluate_inputs(h, B, in, controls, &din); rc != BMPC_OK) return rc;
+  hipStream_t st = h->stream;
+  double* d = h->eval_out.p;
+  const bmpc_grad_out dout = {out->cost ? d + o_c : nullptr, out->grad_u ? d + o_u : nullptr, out->grad_x0 ? d + o_x : nullptr};
+  if (int rc = launch_evaluate_grad(h, B, din, h->controls.p, dout, st); rc != BMPC_OK) return rc;
+  if (out->cost) HIP_TRY(hipMemcpyAsync(out->cost, dout.cost, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (out->grad_x0) HIP_TRY(hipMemcpyAsync(out->grad_x0, dout.grad_x0, n * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (out->grad_u) HIP_TRY(hipMemcpyAsync(out->grad_u, dout.grad_u, n * H * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return BMPC_OK;
 }

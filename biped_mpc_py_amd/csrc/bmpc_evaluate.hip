@@ -24,6 +24,9 @@
 // every output; the selects below keep its values out of every other group.
 //
 // Compiles as plain C++ for tests/emu (BMPC_EMU), where lane_read goes through a shared array between two wave barriers.
+#ifndef BMPC_EVALUATE_HIP
+#define BMPC_EVALUATE_HIP
+
 #ifndef BMPC_EMU
 #include <hip/hip_runtime.h>
 #endif
@@ -107,6 +110,180 @@ __device__ __forceinline__ int group_or(int v, const int lane, const int L) {
   return v;
 }
 
+// ---- the set-up of one (instance, step), shared by evaluate_kernel and evaluate_grad_kernel (bmpc_evaluate_grad.hip): the same
+// expressions in the same order for both, so that what the two kernels have in common (states, cost, the NaN rule) is the same bits
+
+struct EvalLane {            // where a lane stands: its group of L lanes = its instance, its place in the group = its step
+  int L, lane, gl, k;
+  bool in_batch, live;
+  size_t inst, row;
+};
+
+__device__ __forceinline__ EvalLane eval_lane(const int h, const int B) {
+  EvalLane t;
+  t.L = h <= 16 ? 16 : (h <= 32 ? 32 : 64);
+  t.lane = threadIdx.x & 63;
+  t.gl = t.lane & (t.L - 1);                   // place in the group = step
+  const long long grp = ((long long)blockIdx.x * EVAL_NT + threadIdx.x) / t.L;
+  t.in_batch = grp < (long long)B;
+  t.inst = (size_t)(t.in_batch ? grp : (long long)B - 1);
+  t.live = t.gl < h;
+  t.k = t.live ? t.gl : h - 1;
+  t.row = t.inst * (size_t)h + (size_t)t.k;
+  return t;
+}
+
+struct EvalStep {            // what a lane holds of its (instance, step), fp64
+  double xfb[12], u[12], xr[12], fr[6], mu[2];
+  double Rv[9], Iw[9], r[2][3];                // R_inv (REF:160-164 inverted), (Rot' I Rot)^-1, lever arms foot_ref_g - x_ref[3:6]
+  bool singular;                               // reference pitch within fp32 rounding of +-90 degrees
+};
+
+// inputs of this (instance, step), widened; x_ref[:, k] / foot_ref[:, k] supplied, or generated as phase A of the solve forms them
+__device__ __forceinline__ void eval_load(const EvalParams& P, const EvalLane& t,
+                                          const float* __restrict__ x_fb, const float* __restrict__ foot,
+                                          const uint8_t* __restrict__ contact, const int32_t* __restrict__ phase,
+                                          const float* __restrict__ x_cmd, const float* __restrict__ mu_in,
+                                          const float* __restrict__ x_ref, const float* __restrict__ foot_ref,
+                                          const float* __restrict__ controls, EvalStep& s) {
+  const int h = P.h, k = t.k;
+  const size_t inst = t.inst, row = t.row;
+  const double dt = P.dt;
+  double xc[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    s.xfb[i] = (double)x_fb[inst * 12 + i];
+    xc[i] = x_cmd ? (double)x_cmd[inst * 12 + i] : P.x_cmd[i];
+    s.u[i] = (double)controls[row * 12 + i];
+  }
+  if (x_ref) {                                 // x_ref[:, k]: supplied, or REF:61-70 as phase A of the solve forms it
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s.xr[i] = (double)x_ref[row * 12 + i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      if (k == 0) s.xr[i] = s.xfb[i];
+      else if (i < 6) s.xr[i] = (xc[i + 6] != 0.0) ? s.xfb[i] + xc[i + 6] * ((double)k * dt) : xc[i];
+      else s.xr[i] = xc[i];
+    }
+  }
+  if (foot_ref) {                              // foot_ref[:, k]: supplied, or REF:72-109 likewise
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s.fr[i] = (double)foot_ref[row * 6 + i];
+  } else {
+    const int c0 = contact[inst * (size_t)h * 2 + 0], c1 = contact[inst * (size_t)h * 2 + 1];
+    const bool single = (c0 + c1) == 1;        // REF:102
+    const int kk = phase[inst] % P.half;       // REF:101
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s.fr[i] = (double)foot[inst * 6 + i];
+    if (single && k >= P.half - kk) {
+      const bool second = k >= 2 * P.half - kk;
+      const double hor = second ? 0.5 * (double)h * dt : 0.5 * (double)h / 2.0 * dt;                    // REF:74, 78
+      const double fx = s.xfb[3] + s.xfb[9] * hor + P.kv * (s.xfb[3] - xc[3]);
+      const double fy = (second ? s.xfb[10] : s.xfb[4]) + s.xfb[10] * hor + P.kv * (s.xfb[4] - xc[4]);  // REF:87 quirk
+      s.fr[0] = fx; s.fr[1] = fy; s.fr[2] = 0; s.fr[3] = fx; s.fr[4] = fy; s.fr[5] = 0;
+    }
+  }
+  s.mu[0] = mu_in ? (double)mu_in[row * 2 + 0] : P.mu;
+  s.mu[1] = mu_in ? (double)mu_in[row * 2 + 1] : P.mu;
+}
+
+// SRBM step data (REF:148-185) and this step's increments of omega and v: B_k u_k and the gravity column of A_k
+__device__ __forceinline__ void eval_step_model(const EvalParams& P, EvalStep& s, double (&inc)[6]) {
+  const double dt = P.dt;
+  const double* xr = s.xr;
+  const double* u = s.u;
+  double sy, cy, sp, cp, sr, cr;               // REF:151-153: yaw = x[0], pitch = x[1], roll = x[2]
+  sincos(xr[0], &sy, &cy);
+  sincos(xr[1], &sp, &cp);
+  sincos(xr[2], &sr, &cr);
+  s.singular = !(fabs(cp) >= 0x1p-22);
+  // Rot = Rx(roll) Ry(pitch) Rz(yaw)   (scipy 'zyx' extrinsic, REF:154-156)
+  const double Rot[9] = {cp * cy, -cp * sy, sp,
+                         cr * sy + sr * sp * cy, cr * cy - sr * sp * sy, -sr * cp,
+                         sr * sy - cr * sp * cy, sr * cy + cr * sp * sy, cr * cp};
+  double T[9];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+      T[3 * a + b] = P.Iinv[3 * a] * Rot[b] + P.Iinv[3 * a + 1] * Rot[3 + b] + P.Iinv[3 * a + 2] * Rot[6 + b];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+      s.Iw[3 * a + b] = Rot[a] * T[b] + Rot[3 + a] * T[3 + b] + Rot[6 + a] * T[6 + b];   // Rot' Iinv Rot = (Rot' I Rot)^-1
+  const double tp = sp / cp;
+  const double rv[9] = {cy / cp, sy / cp, 0, -sy, cy, 0, cy * tp, sy * tp, 1};           // REF:160-164 inverted
+#pragma unroll
+  for (int q = 0; q < 9; ++q) s.Rv[q] = rv[q];
+  // net torque about the CoM: r_1 x f_1 + r_2 x f_2 + m_1 + m_2, r_g = foot_ref_g - x_ref[3:6]  (REF:174-179)
+  double tau[3] = {u[6] + u[9], u[7] + u[10], u[8] + u[11]};
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const double r[3] = {s.fr[3 * g] - xr[3], s.fr[3 * g + 1] - xr[4], s.fr[3 * g + 2] - xr[5]};
+    const double* f = &u[3 * g];
+    tau[0] += r[1] * f[2] - r[2] * f[1];
+    tau[1] += r[2] * f[0] - r[0] * f[2];
+    tau[2] += r[0] * f[1] - r[1] * f[0];
+    s.r[g][0] = r[0]; s.r[g][1] = r[1]; s.r[g][2] = r[2];
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    inc[a] = dt * (s.Iw[3 * a] * tau[0] + s.Iw[3 * a + 1] * tau[1] + s.Iw[3 * a + 2] * tau[2]);
+    inc[3 + a] = P.kvm * (u[a] + u[3 + a]);                                              // REF:180
+  }
+  inc[5] -= P.g * dt;                                                                    // REF:169
+}
+
+// the recurrence: omega, v after step k from the increments `inc`; then euler, p from the states before step k.  x = state after step k
+__device__ __forceinline__ void eval_recurrence(const EvalParams& P, const EvalLane& t, const EvalStep& s, double (&inc)[6],
+                                                double (&x)[12]) {
+  const double dt = P.dt;
+  group_prefix<6>(inc, t.lane, t.gl, t.L);
+#pragma unroll
+  for (int a = 0; a < 6; ++a) x[6 + a] = s.xfb[6 + a] + inc[a];
+  {
+    double before[6];                          // omega_k, v_k: the lane below's result, x_fb at step 0
+    const int src = (t.lane - 1) & 63;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      const double o = lane_read(x[6 + a], src);
+      before[a] = t.gl > 0 ? o : s.xfb[6 + a];
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      inc[a] = dt * (s.Rv[3 * a] * before[0] + s.Rv[3 * a + 1] * before[1] + s.Rv[3 * a + 2] * before[2]);   // REF:166
+      inc[3 + a] = dt * before[3 + a];                                                                       // REF:167
+    }
+  }
+  group_prefix<6>(inc, t.lane, t.gl, t.L);
+#pragma unroll
+  for (int a = 0; a < 6; ++a) x[a] = s.xfb[a] + inc[a];
+}
+
+// is everything the lanes of this group saw finite, and no reference pitch singular?  (a sum of magnitudes: NaN and Inf both fail
+// the comparison).  Non-zero on every lane of a group that holds a bad live lane.
+__device__ __forceinline__ int eval_bad(const EvalLane& t, const EvalStep& s, const double (&x)[12]) {
+  double mag = fabs(s.mu[0]) + fabs(s.mu[1]);
+#pragma unroll
+  for (int i = 0; i < 12; ++i) mag += fabs(s.u[i]) + fabs(s.xr[i]) + fabs(x[i]);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) mag += fabs(s.fr[i]);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) mag += fabs(s.Rv[q]);
+  return group_or((t.live && (s.singular || !(mag <= 1.7976931348623157e308))) ? 1 : 0, t.lane, t.L);
+}
+
+// cost of this step (REF:278-286 completed): sum_i Q_i (x_i - x_ref_i)^2 + R_i u_i^2, added to `acc`
+__device__ __forceinline__ void eval_step_cost(const EvalParams& P, const EvalStep& s, const double (&x)[12], double& acc) {
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const double e = x[i] - s.xr[i];
+    acc += P.Q[i] * e * e + P.R[i] * s.u[i] * s.u[i];
+  }
+}
+
 __global__ void __launch_bounds__(EVAL_NT)
 evaluate_kernel(const EvalParams P, const int B,
                 const float* __restrict__ x_fb, const float* __restrict__ foot,
@@ -114,146 +291,28 @@ evaluate_kernel(const EvalParams P, const int B,
                 const float* __restrict__ x_cmd, const float* __restrict__ mu_in,
                 const float* __restrict__ x_ref, const float* __restrict__ foot_ref,
                 const float* __restrict__ controls, const EvalOut out) {
-  const int h = P.h;
-  const int L = h <= 16 ? 16 : (h <= 32 ? 32 : 64);
-  const int lane = threadIdx.x & 63;
-  const int gl = lane & (L - 1);               // place in the group = step
-  const long long grp = ((long long)blockIdx.x * EVAL_NT + threadIdx.x) / L;
-  const bool in_batch = grp < (long long)B;
-  const size_t inst = (size_t)(in_batch ? grp : (long long)B - 1);
-  const bool live = gl < h;
-  const int k = live ? gl : h - 1;
-  const size_t row = inst * (size_t)h + (size_t)k;
-  const double dt = P.dt;
+  const EvalLane t = eval_lane(P.h, B);
+  const int L = t.L, lane = t.lane, gl = t.gl;
+  const bool in_batch = t.in_batch, live = t.live;
+  const size_t inst = t.inst, row = t.row;
 
-  // ---- inputs of this (instance, step), widened
-  double xfb[12], xc[12], u[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    xfb[i] = (double)x_fb[inst * 12 + i];
-    xc[i] = x_cmd ? (double)x_cmd[inst * 12 + i] : P.x_cmd[i];
-    u[i] = (double)controls[row * 12 + i];
-  }
-  double xr[12];                               // x_ref[:, k]: supplied, or REF:61-70 as phase A of the solve forms it
-  if (x_ref) {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) xr[i] = (double)x_ref[row * 12 + i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-      if (k == 0) xr[i] = xfb[i];
-      else if (i < 6) xr[i] = (xc[i + 6] != 0.0) ? xfb[i] + xc[i + 6] * ((double)k * dt) : xc[i];
-      else xr[i] = xc[i];
-    }
-  }
-  double fr[6];                                // foot_ref[:, k]: supplied, or REF:72-109 likewise
-  if (foot_ref) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) fr[i] = (double)foot_ref[row * 6 + i];
-  } else {
-    const int c0 = contact[inst * (size_t)h * 2 + 0], c1 = contact[inst * (size_t)h * 2 + 1];
-    const bool single = (c0 + c1) == 1;        // REF:102
-    const int kk = phase[inst] % P.half;       // REF:101
-#pragma unroll
-    for (int i = 0; i < 6; ++i) fr[i] = (double)foot[inst * 6 + i];
-    if (single && k >= P.half - kk) {
-      const bool second = k >= 2 * P.half - kk;
-      const double hor = second ? 0.5 * (double)h * dt : 0.5 * (double)h / 2.0 * dt;            // REF:74, 78
-      const double fx = xfb[3] + xfb[9] * hor + P.kv * (xfb[3] - xc[3]);
-      const double fy = (second ? xfb[10] : xfb[4]) + xfb[10] * hor + P.kv * (xfb[4] - xc[4]);  // REF:87 quirk
-      fr[0] = fx; fr[1] = fy; fr[2] = 0; fr[3] = fx; fr[4] = fy; fr[5] = 0;
-    }
-  }
+  EvalStep s;
+  eval_load(P, t, x_fb, foot, contact, phase, x_cmd, mu_in, x_ref, foot_ref, controls, s);
   const double con[2] = {(double)contact[row * 2 + 0], (double)contact[row * 2 + 1]};
-  const double mu[2] = {mu_in ? (double)mu_in[row * 2 + 0] : P.mu, mu_in ? (double)mu_in[row * 2 + 1] : P.mu};
-
-  // ---- SRBM step data (REF:148-185) and this step's increments of omega and v: B_k u_k and the gravity column of A_k
-  double Rv[9], inc[6];
-  bool singular;
-  {
-    double sy, cy, sp, cp, sr, cr;             // REF:151-153: yaw = x[0], pitch = x[1], roll = x[2]
-    sincos(xr[0], &sy, &cy);
-    sincos(xr[1], &sp, &cp);
-    sincos(xr[2], &sr, &cr);
-    singular = !(fabs(cp) >= 0x1p-22);
-    // Rot = Rx(roll) Ry(pitch) Rz(yaw)   (scipy 'zyx' extrinsic, REF:154-156)
-    const double Rot[9] = {cp * cy, -cp * sy, sp,
-                           cr * sy + sr * sp * cy, cr * cy - sr * sp * sy, -sr * cp,
-                           sr * sy - cr * sp * cy, sr * cy + cr * sp * sy, cr * cp};
-    double T[9], Iw[9];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b)
-        T[3 * a + b] = P.Iinv[3 * a] * Rot[b] + P.Iinv[3 * a + 1] * Rot[3 + b] + P.Iinv[3 * a + 2] * Rot[6 + b];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b)
-        Iw[3 * a + b] = Rot[a] * T[b] + Rot[3 + a] * T[3 + b] + Rot[6 + a] * T[6 + b];   // Rot' Iinv Rot = (Rot' I Rot)^-1
-    const double tp = sp / cp;
-    const double rv[9] = {cy / cp, sy / cp, 0, -sy, cy, 0, cy * tp, sy * tp, 1};         // REF:160-164 inverted
-#pragma unroll
-    for (int q = 0; q < 9; ++q) Rv[q] = rv[q];
-    // net torque about the CoM: r_1 x f_1 + r_2 x f_2 + m_1 + m_2, r_g = foot_ref_g - x_ref[3:6]  (REF:174-179)
-    double tau[3] = {u[6] + u[9], u[7] + u[10], u[8] + u[11]};
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      const double r[3] = {fr[3 * g] - xr[3], fr[3 * g + 1] - xr[4], fr[3 * g + 2] - xr[5]};
-      const double* f = &u[3 * g];
-      tau[0] += r[1] * f[2] - r[2] * f[1];
-      tau[1] += r[2] * f[0] - r[0] * f[2];
-      tau[2] += r[0] * f[1] - r[1] * f[0];
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      inc[a] = dt * (Iw[3 * a] * tau[0] + Iw[3 * a + 1] * tau[1] + Iw[3 * a + 2] * tau[2]);
-      inc[3 + a] = P.kvm * (u[a] + u[3 + a]);                                            // REF:180
-    }
-    inc[5] -= P.g * dt;                                                                  // REF:169
-  }
-
-  // ---- the recurrence: omega, v after step k; then euler, p from the states before step k
-  double x[12];                                // state after step k
-  group_prefix<6>(inc, lane, gl, L);
-#pragma unroll
-  for (int a = 0; a < 6; ++a) x[6 + a] = xfb[6 + a] + inc[a];
-  {
-    double before[6];                          // omega_k, v_k: the lane below's result, x_fb at step 0
-    const int src = (lane - 1) & 63;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      const double o = lane_read(x[6 + a], src);
-      before[a] = gl > 0 ? o : xfb[6 + a];
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      inc[a] = dt * (Rv[3 * a] * before[0] + Rv[3 * a + 1] * before[1] + Rv[3 * a + 2] * before[2]);   // REF:166
-      inc[3 + a] = dt * before[3 + a];                                                                 // REF:167
-    }
-  }
-  group_prefix<6>(inc, lane, gl, L);
-#pragma unroll
-  for (int a = 0; a < 6; ++a) x[a] = xfb[a] + inc[a];
-
-  // ---- is everything this lane saw finite?  (a sum of magnitudes: NaN and Inf both fail the comparison)
-  double mag = fabs(mu[0]) + fabs(mu[1]);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) mag += fabs(u[i]) + fabs(xr[i]) + fabs(x[i]);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) mag += fabs(fr[i]);
-#pragma unroll
-  for (int q = 0; q < 9; ++q) mag += fabs(Rv[q]);
-  const int bad = group_or((live && (singular || !(mag <= 1.7976931348623157e308))) ? 1 : 0, lane, L);
+  double inc[6], x[12];                        // x = state after step k
+  eval_step_model(P, s, inc);
+  eval_recurrence(P, t, s, inc, x);
+  const int bad = eval_bad(t, s, x);
+  const double* xfb = s.xfb;
+  const double* u = s.u;
+  const double* xr = s.xr;
+  const double* mu = s.mu;
 
   // ---- cost of this step; the constant between cost and objective
   double sums[2] = {0.0, P.Q[12]};             // (the 13th state is 1 and so is its reference: no cost, Q[12] in the constant)
+  eval_step_cost(P, s, x, sums[0]);
 #pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const double e = x[i] - xr[i];
-    sums[0] += P.Q[i] * e * e + P.R[i] * u[i] * u[i];
-    sums[1] += P.Q[i] * xr[i] * xr[i];
-  }
+  for (int i = 0; i < 12; ++i) sums[1] += P.Q[i] * xr[i] * xr[i];
   if (!live) { sums[0] = 0.0; sums[1] = 0.0; }
   group_sum<2>(sums, lane, L);
 
@@ -288,10 +347,10 @@ evaluate_kernel(const EvalParams P, const int B,
   if (!in_batch) return;
   const double nan = __builtin_nan("");
   if (out.states && live) {
-    double* s = out.states + row * 13;
+    double* so = out.states + row * 13;
 #pragma unroll
-    for (int i = 0; i < 12; ++i) s[i] = bad ? nan : x[i];
-    s[12] = bad ? nan : 1.0;
+    for (int i = 0; i < 12; ++i) so[i] = bad ? nan : x[i];
+    so[12] = bad ? nan : 1.0;
   }
   if (gl == 0) {
     if (out.cost) out.cost[inst] = bad ? nan : sums[0];
@@ -304,3 +363,5 @@ evaluate_kernel(const EvalParams P, const int B,
 }
 
 }  // namespace bmpc
+
+#endif  // BMPC_EVALUATE_HIP

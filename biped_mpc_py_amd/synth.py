@@ -69,7 +69,8 @@ CONFIGS = {
 # The kernel sources, in csrc/: everything that is compiled into libbmpc.so and into the emulation libraries of tests/emu.  THE list:
 # the build, the source hash below and the emulation drivers read it (kernel_source_paths), so that an edit of any of these files
 # rebuilds all of them.  bmpc_capi.hip, the first, is the translation unit that includes the others.
-KERNEL_SOURCES = ("bmpc_capi.hip", "bmpc_kernels.hip", "bmpc_stage.hip", "bmpc_lowlevel.hip", "bmpc_evaluate.hip", "bmpc_model.hip")
+KERNEL_SOURCES = ("bmpc_capi.hip", "bmpc_kernels.hip", "bmpc_stage.hip", "bmpc_lowlevel.hip", "bmpc_evaluate.hip", "bmpc_evaluate_grad.hip",
+                  "bmpc_model.hip")
 
 
 def kernel_source_paths():

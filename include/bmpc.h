@@ -391,6 +391,41 @@ int bmpc_evaluate_device(bmpc_handle h, int B, const bmpc_inputs* in, const floa
 int bmpc_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out);
 
 /*
+ * Gradient of the evaluated cost (added under ABI 13; BMPC_ABI_VERSION is unchanged because the addition is purely additive --
+ * no existing entry, struct or meaning moves -- so a caller detects it by the symbol, e.g. dlsym(lib, "bmpc_evaluate_grad_device")).
+ * `cost` above is an exact quadratic in the controls; its gradient is one adjoint sweep over the horizon, in the same launch shape
+ * as the evaluation.  Uses: first-order refinement of a foreign plan, a differentiable MPC cost inside a training loop, the
+ * sensitivity of a plan's cost to the measured state, and an optimality check of a solver's answer that needs no multipliers
+ * (at an optimum U*, grad_u . (V - U*) >= 0 for every feasible V).  Inputs: those of bmpc_evaluate*.
+ * outputs, per instance, each optional (NULL = not wanted; at least one must be given), fp64:
+ *   cost     the same value and the same bits as bmpc_evaluate*'s `cost` on the same inputs
+ *   grad_u   [h][12]: d cost / d controls, row k = 2 diag(R) u_k + B_k' lambda_k with the costates
+ *            lambda_k = d cost / d x_{k+1} = 2 diag(Q) (x_{k+1} - x_ref[:, k]) + A_{k+1}' lambda_{k+1} (nothing above k = h - 1),
+ *            A_k / B_k of REF:148-185 as the evaluation linearises them
+ *   grad_x0  [12]: d cost / d x_fb THROUGH THE INITIAL CONDITION x_0 = [x_fb; 1] ONLY, A_0' lambda_0.  The references, the lever
+ *            arms and the linearisation are held fixed, whether they were supplied or generated: generated references (and the
+ *            line-foot body axes, which do not enter the cost) depend on x_fb, and that dependence is deliberately NOT
+ *            differentiated.  With supplied references this is the full derivative.
+ * The cost is quadratic in the controls, so grad_u(U + D) - grad_u(U) is the Hessian-vector product H D; there is no separate entry.
+ * Arithmetic, bad instances (NaN in every output of that instance, no other instance touched), independence of B and of the place
+ * in the batch: as for the evaluation.
+ *   bmpc_evaluate_grad_device   DEVICE pointers, asynchronous on `stream` (same rules as bmpc_evaluate_device); nothing is copied
+ *   bmpc_evaluate_grad          HOST pointers, synchronous (staged through the handle's own stream)
+ * A NULL handle, descriptor, `controls` or `out`, all three outputs NULL, foot == NULL without foot_ref, or B outside
+ * [0, max_batch] is BMPC_ERR_INVALID; the NULL checks come before a device is touched; B = 0 succeeds.  Every supported horizon
+ * (1 .. 40); the handle's kernel family plays no part; the handle's parameter block is read and none of its per-solve state is
+ * touched (as for bmpc_evaluate*).  bmpc_eval_out is unchanged.
+ */
+typedef struct bmpc_grad_out {
+  double* cost;        /* [B] or NULL */
+  double* grad_u;      /* [B][h][12] or NULL */
+  double* grad_x0;     /* [B][12] or NULL */
+} bmpc_grad_out;
+int bmpc_evaluate_grad_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls,
+                              const bmpc_grad_out* out, void* stream);
+int bmpc_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_grad_out* out);
+
+/*
  * The step either side of the MPC solve, batched; HOST pointers, synchronous.
  *   bmpc_foot_position_world  replaces getFootPositionWorld (REF:406-424, with getFootPositionBody REF:367-404):
  *       x_fb [B][12], q [B][10] joint angles  ->  pf_w [B][6]
