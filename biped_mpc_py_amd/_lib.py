@@ -21,6 +21,7 @@ EXPORTS = (
     "bmpc_debug_assemble", "bmpc_debug_set_profile", "bmpc_last_kernel_ms",
     "bmpc_solve_inputs_f64", "bmpc_solve_inputs_device", "bmpc_debug_assemble_inputs",
     "bmpc_evaluate_device", "bmpc_evaluate", "bmpc_evaluate_grad_device", "bmpc_evaluate_grad",
+    "bmpc_certify_device", "bmpc_certify",
     "bmpc_foot_position_world", "bmpc_foot_position_world_device",
     "bmpc_low_level_control", "bmpc_low_level_control_device",
     "bmpc_gait_default", "bmpc_contact_sequence", "bmpc_contact_sequence_device",
@@ -52,6 +53,11 @@ class CEvalOut(C.Structure):
 class CGradOut(C.Structure):
     """`bmpc_grad_out` of include/bmpc.h: the outputs of a cost gradient, each optional (NULL: not wanted)."""
     _fields_ = [(n, C.c_void_p) for n in ("cost", "grad_u", "grad_x0")]
+
+
+class CCertOut(C.Structure):
+    """`bmpc_cert_out` of include/bmpc.h: the outputs of a KKT certificate, each optional (NULL: not wanted)."""
+    _fields_ = [(n, C.c_void_p) for n in ("lam", "resid", "summary", "n_active", "status")]
 
 
 class BmpcError(RuntimeError):
@@ -147,6 +153,8 @@ def load():
     lib.bmpc_evaluate.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CEvalOut)]
     lib.bmpc_evaluate_grad_device.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CGradOut), vp]
     lib.bmpc_evaluate_grad.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CGradOut)]
+    lib.bmpc_certify_device.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.c_double, C.POINTER(CCertOut), vp]
+    lib.bmpc_certify.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.c_double, C.POINTER(CCertOut)]
     lib.bmpc_foot_position_world.argtypes = [vp, ip, vp, vp, vp]
     lib.bmpc_foot_position_world_device.argtypes = [vp, ip, vp, vp, vp, vp]
     lib.bmpc_low_level_control.argtypes = [vp, ip] + [vp] * 8

@@ -122,6 +122,21 @@ def _controls_f32(controls, h, B=None):
     return np.ascontiguousarray(c, np.float32)
 
 
+ACT_TOL = 1e-4          # default activity tolerance of `certify`: the tolerance the solver's controls are held to against the oracle
+
+
+def duals_to_reference_order(lam):
+    """Multipliers as `certify` returns them, (..., h, 36) in the order of a step's rows, -> (..., 36h) in the row order of G at
+    REF:273: friction row 8k + r (r < 8), box rows 8h + 24k + (r - 8), line-foot rows 32h + 4k + (r - 32)."""
+    lam = np.asarray(lam)
+    if lam.ndim < 2 or lam.shape[-1] != 36:
+        raise ValueError(f"lam must have shape (..., h, 36), got {lam.shape}")
+    h = lam.shape[-2]
+    lead = lam.shape[:-2]
+    return np.concatenate([lam[..., 0:8].reshape(lead + (8 * h,)), lam[..., 8:32].reshape(lead + (24 * h,)),
+                           lam[..., 32:36].reshape(lead + (4 * h,))], -1)
+
+
 def _ptr(a):
     """Address of a NumPy array as an integer (what a `c_void_p` parameter takes; building a ctypes pointer object per argument
     costs ~2 us each, fourteen of them per solve)."""
@@ -225,7 +240,7 @@ class BatchSolver:
         return B, x_fb, foot, contact, phase, x_cmd, mu
 
     def solve(self, x_fb, foot, contact, phase, x_cmd=None, mu=None, want_states=True, out=None, x_ref=None, foot_ref=None,
-              evaluate=False):
+              evaluate=False, certify=False, act_tol=ACT_TOL):
         """Host arrays in, host arrays out (fp32 over PCIe, fp64 returned -- the reference's dtype, REF:300-304; the
         widening happens inside `bmpc_solve_batch_f64` while the results are unpacked, overlapped with the solve).  Returns
         (states (B,h,13) | None, controls (B,h,12), info).  `out`: optional (states | None, controls) fp64 C-contiguous
@@ -233,7 +248,9 @@ class BatchSolver:
         `x_ref` (B,h,12) / `foot_ref` (B,h,6): references to track instead of the generated ones (`bmpc_solve_inputs_f64`,
         include/bmpc.h; kernel layout, row j = step j); `foot` may then be None if `foot_ref` is given.
         `evaluate=True`: `info` gains `cost` (B,), `objective` (B,), `violation` (B,4) of the returned controls (those of the rescue
-        pass where it ran), as `evaluate` gives them; by default `info` keeps exactly its four keys."""
+        pass where it ran), as `evaluate` gives them; by default `info` keeps exactly its four keys.
+        `certify=True`: `info` gains `kkt`, the KKT certificate of the returned controls as `certify` gives it under `act_tol`:
+        dict(stationarity, primal_ineq, complementarity, grad_scale (B,) each, n_active (B,), status (B,), lam (B,h,36))."""
         B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
         x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h)
         if foot is None and foot_ref is None:
@@ -267,6 +284,9 @@ class BatchSolver:
         if evaluate:
             ev = self.evaluate(x_fb, foot, contact, phase, controls, x_cmd=x_cmd, mu=mu, x_ref=x_ref, foot_ref=foot_ref)
             info.update(cost=ev["cost"], objective=ev["objective"], violation=ev["violation"])
+        if certify:
+            ce = self.certify(x_fb, foot, contact, phase, controls, x_cmd=x_cmd, mu=mu, x_ref=x_ref, foot_ref=foot_ref, act_tol=act_tol)
+            info["kkt"] = {k: ce[k] for k in ("stationarity", "primal_ineq", "complementarity", "grad_scale", "n_active", "status", "lam")}
         return states, controls, info
 
     def evaluate(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None, want_states=False):
@@ -312,6 +332,34 @@ class BatchSolver:
         inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
         go = _lib.CGradOut(_ptr(res["cost"]), _ptr(res["grad_u"]), _ptr(res["grad_x0"]))
         _lib.check(self._lib.bmpc_evaluate_grad(self._h, B, C.byref(inp), _ptr(c32), C.byref(go)))
+        return res
+
+    def certify(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None, act_tol=ACT_TOL):
+        """KKT certificate of GIVEN control sequences (`bmpc_certify`, include/bmpc.h): arguments as `evaluate_grad` takes them, and
+        `act_tol`: an inequality row with slack = b - C u is active iff slack <= act_tol (1 + |b|); only active rows may carry a
+        multiplier.  Returns NumPy arrays: lam (B,h,36) fp64, the multipliers >= 0 in the row order of a step (0..7 friction, 8..19
+        upper bounds, 20..31 lower bounds, 32..35 line foot; `duals_to_reference_order` gives the reference's order); resid (B,h,12),
+        `evaluate_grad`'s grad_u + C' lam; summary (B,4) and its columns stationarity = max |resid|, primal_ineq = the largest
+        violation (the maximum of `evaluate`'s four, same bits), complementarity = max |lam_i slack_i|, grad_scale = max |grad_u|
+        (stationarity / grad_scale is the relative figure); n_active (B,) int32; status (B,) int32: 0 converged, 1 an iteration cap
+        was reached (the residuals are valid, only not the smallest), 2 bad instance (NaN in the fp64 outputs, n_active -1)."""
+        c32 = _controls_f32(controls, self.h)
+        B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
+        if c32.shape[0] != B:
+            raise ValueError(f"controls must have shape ({B}, {self.h}, 12), got {c32.shape}")
+        x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h, finite=False)
+        if foot is None and foot_ref is None:
+            raise ValueError("foot is required unless foot_ref is given")
+        act_tol = float(act_tol)
+        if act_tol != act_tol:
+            raise ValueError("act_tol must not be NaN")
+        res = dict(lam=np.empty((B, self.h, 36), np.float64), resid=np.empty((B, self.h, 12), np.float64),
+                   summary=np.empty((B, 4), np.float64), n_active=np.empty(B, np.int32), status=np.empty(B, np.int32))
+        inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
+        co = _lib.CCertOut(_ptr(res["lam"]), _ptr(res["resid"]), _ptr(res["summary"]), _ptr(res["n_active"]), _ptr(res["status"]))
+        _lib.check(self._lib.bmpc_certify(self._h, B, C.byref(inp), _ptr(c32), act_tol, C.byref(co)))
+        for i, k in enumerate(("stationarity", "primal_ineq", "complementarity", "grad_scale")):
+            res[k] = res["summary"][:, i]
         return res
 
     def _io_views(self, B, with_x_cmd, with_mu, with_states):
@@ -517,6 +565,46 @@ class BatchSolver:
         go = _lib.CGradOut(chk(cost, torch.float64, (B,)), chk(grad_u, torch.float64, (B, h, 12)), chk(grad_x0, torch.float64, (B, 12)))
         _lib.check(self._lib.bmpc_evaluate_grad_device(self._h, B, C.byref(inp), chk(controls, torch.float32, (B, h, 12)), C.byref(go), st))
         return dict(cost=cost, grad_u=grad_u, grad_x0=grad_x0)
+
+    def certify_device(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None,
+                       lam=None, resid=None, summary=None, n_active=None, status=None, act_tol=ACT_TOL, stream=None):
+        """`certify` on CUDA(HIP) torch tensors of this solver's device (`bmpc_certify_device`): inputs as `evaluate_grad_device`
+        takes them -- e.g. the `controls` tensor a `solve_device` on the same stream has just been asked to fill: no synchronisation
+        is needed in between.  Outputs are tensors lam (B,h,36), resid (B,h,12), summary (B,4) float64, n_active (B,), status (B,)
+        int32, allocated where not passed.  Asynchronous on `stream` (default: torch's current stream); nothing crosses PCIe.
+        Returns dict(lam, resid, summary, n_active, status)."""
+        import torch
+        B = x_fb.shape[0]
+        h = self.h
+        dev = x_fb.device
+
+        def chk(t, dtype, shape):
+            if t is None:
+                return None
+            if t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"expected contiguous {dtype} tensor of shape {shape} on {dev}")
+            return t.data_ptr()
+
+        if dev.type != "cuda" or dev.index != self.device:
+            raise ValueError(f"tensors must live on cuda:{self.device}")
+        act_tol = float(act_tol)
+        if act_tol != act_tol:
+            raise ValueError("act_tol must not be NaN")
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        lam = new((B, h, 36), torch.float64) if lam is None else lam
+        resid = new((B, h, 12), torch.float64) if resid is None else resid
+        summary = new((B, 4), torch.float64) if summary is None else summary
+        n_active = new((B,), torch.int32) if n_active is None else n_active
+        status = new((B,), torch.int32) if status is None else status
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        inp = _lib.CInputs(chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)),
+                           chk(contact, torch.uint8, (B, h, 2)), chk(phase, torch.int32, (B,)),
+                           chk(x_cmd, torch.float32, (B, 12)), chk(mu, torch.float32, (B, h, 2)),
+                           chk(x_ref, torch.float32, (B, h, 12)), chk(foot_ref, torch.float32, (B, h, 6)))
+        co = _lib.CCertOut(chk(lam, torch.float64, (B, h, 36)), chk(resid, torch.float64, (B, h, 12)), chk(summary, torch.float64, (B, 4)),
+                           chk(n_active, torch.int32, (B,)), chk(status, torch.int32, (B,)))
+        _lib.check(self._lib.bmpc_certify_device(self._h, B, C.byref(inp), chk(controls, torch.float32, (B, h, 12)), act_tol, C.byref(co), st))
+        return dict(lam=lam, resid=resid, summary=summary, n_active=n_active, status=status)
 
     def cost_torch(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None):
         """`evaluate`'s cost as a differentiable torch value: float64 tensor (B,) on the device, with gradients to `controls` (B,h,12)
@@ -808,6 +896,42 @@ def evaluate_grad_mpc(x_fb, t, foot, mpc, biped, contact, controls, half=None, d
                                 x_ref=None if x_ref is None else np.asarray(x_ref)[None],
                                 foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None])
     return dict(cost=float(r["cost"][0]), grad_u=r["grad_u"][0], grad_x0=r["grad_x0"][0])
+
+
+def certify_mpc_batch(x_fb, t, foot, contact, controls, mpc=None, biped=None, x_cmd=None, mu=None, phase=None, half=None,
+                      device=0, x_ref=None, foot_ref=None, act_tol=ACT_TOL):
+    """KKT certificate of given control sequences: `evaluate_grad_mpc_batch`'s call surface (references in the reference's
+    orientation, the cached handle per horizon and device) plus `act_tol`.  Returns the dict of `BatchSolver.certify`."""
+    from .params import MPC
+    mpc = mpc if mpc is not None else MPC()
+    c32 = _controls_f32(controls, int(mpc.h))
+    xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
+    if float(act_tol) != float(act_tol):
+        raise ValueError("act_tol must not be NaN")
+    solver = _cached_solver(mpc, biped, half, device, None)
+    if phase is None:
+        phase = phase_indices(t, mpc.dt, mpc.h)
+    return solver.certify(x_fb, foot, contact, phase, c32, x_cmd=x_cmd, mu=mu, x_ref=xr, foot_ref=fr, act_tol=act_tol)
+
+
+def certify_mpc(x_fb, t, foot, mpc, biped, contact, controls, half=None, device=0, x_ref=None, foot_ref=None, act_tol=ACT_TOL):
+    """`certify_mpc_batch` for one instance with `evaluate_mpc`'s arguments -- e.g. on what `solve_mpc` returned.  Returns
+    dict(lam (h,36), resid (h,12), summary (4,), stationarity, primal_ineq, complementarity, grad_scale floats, n_active, status ints)."""
+    h = int(mpc.h)
+    c = np.asarray(controls)
+    if c.shape != (h, 12):
+        raise ValueError(f"controls must have shape ({h}, 12), got {c.shape}")
+    contact = np.asarray(contact)
+    if contact.ndim != 2 or contact.shape[1] != 2 or contact.shape[0] < h:
+        raise ValueError(f"contact must have at least {h} rows of 2 (REF:239-249 indexes contact[k] for k < h)")
+    r = certify_mpc_batch(np.asarray(x_fb, float).reshape(1, 12), [t], np.asarray(foot, float).reshape(1, 6), contact[None, :h, :],
+                          c[None], mpc=mpc, biped=biped, half=half, device=device,
+                          x_ref=None if x_ref is None else np.asarray(x_ref)[None],
+                          foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None], act_tol=act_tol)
+    out = dict(lam=r["lam"][0], resid=r["resid"][0], summary=r["summary"][0], n_active=int(r["n_active"][0]), status=int(r["status"][0]))
+    for k in ("stationarity", "primal_ineq", "complementarity", "grad_scale"):
+        out[k] = float(r[k][0])
+    return out
 
 
 def reference_trajectories_batch(x_fb, t, foot, contact, mpc=None, biped=None, x_cmd=None, phase=None, half=None, device=0):

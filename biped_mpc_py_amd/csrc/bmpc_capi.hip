@@ -6,6 +6,7 @@
 #include "bmpc_lowlevel.hip"
 #include "bmpc_evaluate.hip"
 #include "bmpc_evaluate_grad.hip"
+#include "bmpc_certify.hip"
 
 #include <chrono>
 #include <cmath>
@@ -1172,6 +1173,56 @@ int bmpc_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs* in, const float*
   if (out->cost) HIP_TRY(hipMemcpyAsync(out->cost, dout.cost, n * sizeof(double), hipMemcpyDeviceToHost, st));
   if (out->grad_x0) HIP_TRY(hipMemcpyAsync(out->grad_x0, dout.grad_x0, n * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
   if (out->grad_u) HIP_TRY(hipMemcpyAsync(out->grad_u, dout.grad_u, n * H * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return BMPC_OK;
+}
+
+// ---- KKT certificate of given controls (bmpc_certify.hip): the entries of the evaluation with an activity tolerance and other outputs
+
+static int check_certify(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol, const bmpc_cert_out* out) {
+  if (act_tol != act_tol) return fail(BMPC_ERR_INVALID, "act_tol is NaN");
+  return check_evaluate_args(h, B, in, controls, out, out && (out->lam || out->resid || out->summary || out->n_active || out->status),
+                             "null bmpc_cert_out", "bmpc_cert_out: at least one of lam, resid, summary, n_active, status must be non-null");
+}
+
+static int launch_certify(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, double act_tol, const bmpc_cert_out& out,
+                          hipStream_t st) {
+  const bmpc::CertOut o = {out.lam, out.resid, out.summary, out.n_active, out.status};
+  hipLaunchKernelGGL(bmpc::certify_kernel, evaluate_grid(h, B), dim3(bmpc::EVAL_NT), 0, st,
+                     bmpc::eval_params(h->params, h->dev.Iinv), B, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd, in.mu, in.x_ref,
+                     in.foot_ref, controls, act_tol, o);
+  HIP_TRY(hipGetLastError());
+  return BMPC_OK;
+}
+
+int bmpc_certify_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol, const bmpc_cert_out* out,
+                        void* stream) {
+  if (int rc = check_certify(h, B, in, controls, act_tol, out); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return launch_certify(h, B, *in, controls, act_tol, *out, pick_stream(h, stream));
+}
+
+int bmpc_certify(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol, const bmpc_cert_out* out) {
+  if (int rc = check_certify(h, B, in, controls, act_tol, out); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t n = (size_t)B, H = (size_t)h->dev.h;
+  // the two int32 outputs share one double each pair of instances at the end of the fp64 block
+  const size_t o_s = 0, o_r = o_s + (out->summary ? n * 4 : 0), o_l = o_r + (out->resid ? n * H * 12 : 0),
+               o_n = o_l + (out->lam ? n * H * 36 : 0), o_t = o_n + (out->n_active ? (n + 1) / 2 : 0),
+               tot = o_t + (out->status ? (n + 1) / 2 : 0);
+  HIP_TRY(h->eval_out.ensure(tot));
+  bmpc_inputs din;
+  if (int rc = stage_evaluate_inputs(h, B, in, controls, &din); rc != BMPC_OK) return rc;
+  hipStream_t st = h->stream;
+  double* d = h->eval_out.p;
+  const bmpc_cert_out dout = {out->lam ? d + o_l : nullptr, out->resid ? d + o_r : nullptr, out->summary ? d + o_s : nullptr,
+                              out->n_active ? (int32_t*)(d + o_n) : nullptr, out->status ? (int32_t*)(d + o_t) : nullptr};
+  if (int rc = launch_certify(h, B, din, h->controls.p, act_tol, dout, st); rc != BMPC_OK) return rc;
+  if (out->summary) HIP_TRY(hipMemcpyAsync(out->summary, dout.summary, n * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (out->resid) HIP_TRY(hipMemcpyAsync(out->resid, dout.resid, n * H * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (out->lam) HIP_TRY(hipMemcpyAsync(out->lam, dout.lam, n * H * 36 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (out->n_active) HIP_TRY(hipMemcpyAsync(out->n_active, dout.n_active, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (out->status) HIP_TRY(hipMemcpyAsync(out->status, dout.status, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return BMPC_OK;
 }

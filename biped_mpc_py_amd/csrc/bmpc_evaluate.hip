@@ -284,6 +284,34 @@ __device__ __forceinline__ void eval_step_cost(const EvalParams& P, const EvalSt
   }
 }
 
+// rows of Aqp z <= bqp of this step (REF:273-274): the largest positive part per class -- friction, force box, moment box, line foot
+__device__ __forceinline__ void eval_step_violation(const EvalParams& P, const EvalStep& s, const double (&con)[2], double (&viol)[4]) {
+  const double* xfb = s.xfb;
+  const double* u = s.u;
+  const double* mu = s.mu;
+  viol[0] = 0.0; viol[1] = 0.0; viol[2] = 0.0; viol[3] = 0.0;
+  // body axes of the line-foot rows: columns y and z of R = eul2rotm(x_fb[0:3]) = Rz(e2) Ry(e1) Rx(e0)  (REF:124-138, 193, 259-262)
+  double s0, c0, s1, c1, s2, c2, ey[3], ez[3];
+  sincos(xfb[0], &s0, &c0);
+  sincos(xfb[1], &s1, &c1);
+  sincos(xfb[2], &s2, &c2);
+  body_axes(s0, c0, s1, c1, s2, c2, ey, ez);
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const double* f = &u[3 * g];
+    const double* m = &u[6 + 3 * g];
+    const double mf = mu[g] * f[2];
+    viol[0] = fmax(viol[0], fmax(fmax(f[0] - mf, f[1] - mf), fmax(-f[0] - mf, -f[1] - mf)));          // REF:220-229
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {                                                                      // REF:235-251
+      viol[1] = fmax(viol[1], fmax(f[a] - con[g] * P.f_max[a], con[g] * P.f_min[a] - f[a]));
+      viol[2] = fmax(viol[2], fmax(m[a] - con[g] * P.tau_max[a], con[g] * P.tau_min[a] - m[a]));
+    }
+    const double fz = ez[0] * f[0] + ez[1] * f[1] + ez[2] * f[2], my = ey[0] * m[0] + ey[1] * m[1] + ey[2] * m[2];
+    viol[3] = fmax(viol[3], fmax(my - P.lh * fz, -my - P.lt * fz));                                    // REF:259-262
+  }
+}
+
 __global__ void __launch_bounds__(EVAL_NT)
 evaluate_kernel(const EvalParams P, const int B,
                 const float* __restrict__ x_fb, const float* __restrict__ foot,
@@ -303,10 +331,7 @@ evaluate_kernel(const EvalParams P, const int B,
   eval_step_model(P, s, inc);
   eval_recurrence(P, t, s, inc, x);
   const int bad = eval_bad(t, s, x);
-  const double* xfb = s.xfb;
-  const double* u = s.u;
   const double* xr = s.xr;
-  const double* mu = s.mu;
 
   // ---- cost of this step; the constant between cost and objective
   double sums[2] = {0.0, P.Q[12]};             // (the 13th state is 1 and so is its reference: no cost, Q[12] in the constant)
@@ -317,29 +342,8 @@ evaluate_kernel(const EvalParams P, const int B,
   group_sum<2>(sums, lane, L);
 
   // ---- rows of Aqp z <= bqp of this step: the largest positive part per class
-  double viol[4] = {0.0, 0.0, 0.0, 0.0};
-  {
-    // body axes of the line-foot rows: columns y and z of R = eul2rotm(x_fb[0:3]) = Rz(e2) Ry(e1) Rx(e0)  (REF:124-138, 193, 259-262)
-    double s0, c0, s1, c1, s2, c2, ey[3], ez[3];
-    sincos(xfb[0], &s0, &c0);
-    sincos(xfb[1], &s1, &c1);
-    sincos(xfb[2], &s2, &c2);
-    body_axes(s0, c0, s1, c1, s2, c2, ey, ez);
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      const double* f = &u[3 * g];
-      const double* m = &u[6 + 3 * g];
-      const double mf = mu[g] * f[2];
-      viol[0] = fmax(viol[0], fmax(fmax(f[0] - mf, f[1] - mf), fmax(-f[0] - mf, -f[1] - mf)));          // REF:220-229
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {                                                                      // REF:235-251
-        viol[1] = fmax(viol[1], fmax(f[a] - con[g] * P.f_max[a], con[g] * P.f_min[a] - f[a]));
-        viol[2] = fmax(viol[2], fmax(m[a] - con[g] * P.tau_max[a], con[g] * P.tau_min[a] - m[a]));
-      }
-      const double fz = ez[0] * f[0] + ez[1] * f[1] + ez[2] * f[2], my = ey[0] * m[0] + ey[1] * m[1] + ey[2] * m[2];
-      viol[3] = fmax(viol[3], fmax(my - P.lh * fz, -my - P.lt * fz));                                    // REF:259-262
-    }
-  }
+  double viol[4];
+  eval_step_violation(P, s, con, viol);
   if (!live) { viol[0] = 0.0; viol[1] = 0.0; viol[2] = 0.0; viol[3] = 0.0; }
   group_max<4>(viol, lane, L);
 

@@ -69,6 +69,8 @@ evaluate_grad_kernel(const EvalParams P, const int B,
   if (!t.live) cost[0] = 0.0;
   group_sum<1>(cost, lane, L);
 
+  // (From here to the stores: bmpc_certify.hip holds this backward pass a second time, statement for statement, as eval_adjoint --
+  //  sharing one function moved this kernel's `cost` by an ulp.  An edit here goes there too; tests/test_gpu_certify.py compares the bits.)
   // ---- backward, round 1: lambda_eul, lambda_p = suffix sums of 2 Q e  (lanes past the horizon hold clones: zero by a select)
   double lam[12];                              // lambda_k in the order of the state: euler, p, omega, v
 #pragma unroll

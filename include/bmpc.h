@@ -426,6 +426,49 @@ int bmpc_evaluate_grad_device(bmpc_handle h, int B, const bmpc_inputs* in, const
 int bmpc_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_grad_out* out);
 
 /*
+ * KKT certificate of given controls (added under ABI 13; BMPC_ABI_VERSION is unchanged because the addition is purely additive, so a
+ * caller detects it by the symbol, e.g. dlsym(lib, "bmpc_certify_device")).  Answers, on the device and from the controls alone: is
+ * this point the constrained optimum of REF:187-297, how far off is it, and which inequality rows bind at what price.
+ * Every inequality row of REF:273-274 touches the controls of one leg at one step, and grad_u above is the gradient of the condensed
+ * cost, so stationarity grad_u + C' lam = 0, lam >= 0 splits into 2 h non-negative least-squares problems per instance with 6
+ * unknown directions and at most 18 candidate rows each (Lawson-Hanson, fp64, at most 3 x 18 least-squares solves per leg).
+ * Inputs: those of bmpc_evaluate*, and `act_tol`: a row with slack = b - C u is ACTIVE iff slack <= act_tol (1 + |b|); only active
+ * rows may carry a multiplier (a negative act_tol activates no feasible row).  act_tol must not be NaN.
+ * The 36 rows of step k, in the reference's order:  0..7 friction (leg 0 then leg 1, each (+x, +y, -x, -y) - mu z, REF:220-232),
+ * 8..19 upper bounds +u <= ub (u = [f1 f2 m1 m2], bounds scaled by contact, REF:235-251), 20..31 lower bounds -u <= -lb,
+ * 32..35 line foot (leg 0 then leg 1, REF:254-271).  Row 8k + r of G at REF:273 is friction row r of step k, 8h + 24k + r box row
+ * r, 32h + 4k + r line-foot row r.
+ * outputs, per instance, each optional (NULL = not wanted; at least one must be given):
+ *   lam      [h][36] fp64: the multipliers, >= 0, exactly 0 on rows that are not active.  Unique where the active rows of a leg are
+ *            linearly independent; elsewhere (a swing leg pinned at 0, tau_max[0] = 0) one valid choice
+ *   resid    [h][12] fp64: grad_u + C' lam, the stationarity residual (unique: the distance of -grad_u to the cone of active rows)
+ *   summary  [4] fp64: stationarity = max |resid|; primal_ineq = the largest positive part of C u - b (the maximum of
+ *            bmpc_evaluate*'s four `violation` entries, same bits); complementarity = max |lam_i slack_i|; grad_scale = max |grad_u|
+ *            (stationarity / grad_scale is the relative figure)
+ *   n_active int32: the number of active rows
+ *   status   int32: 0 = every least-squares problem converged, 1 = the cap on solves was reached on some leg (lam is still >= 0 and
+ *            supported on active rows, so the residuals are valid, only not the smallest), 2 = bad instance
+ * Bad instances (as for the evaluation): NaN in every fp64 output, n_active = -1, status = 2; no other instance is touched.
+ * Independence of B and of the place in the batch: as for the evaluation.
+ *   bmpc_certify_device   DEVICE pointers, asynchronous on `stream` (same rules as bmpc_evaluate_device); nothing is copied
+ *   bmpc_certify          HOST pointers, synchronous (staged through the handle's own stream)
+ * A NULL handle, descriptor, `controls` or `out`, all five outputs NULL, a NaN act_tol, foot == NULL without foot_ref, or B outside
+ * [0, max_batch] is BMPC_ERR_INVALID; the NULL checks come before a device is touched; B = 0 succeeds.  Every supported horizon
+ * (1 .. 40); the handle's kernel family plays no part; the handle's parameter block is read and none of its per-solve state is
+ * touched.
+ */
+typedef struct bmpc_cert_out {
+  double* lam;         /* [B][h][36] or NULL */
+  double* resid;       /* [B][h][12] or NULL */
+  double* summary;     /* [B][4] or NULL */
+  int32_t* n_active;   /* [B] or NULL */
+  int32_t* status;     /* [B] or NULL */
+} bmpc_cert_out;
+int bmpc_certify_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol,
+                        const bmpc_cert_out* out, void* stream);
+int bmpc_certify(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol, const bmpc_cert_out* out);
+
+/*
  * The step either side of the MPC solve, batched; HOST pointers, synchronous.
  *   bmpc_foot_position_world  replaces getFootPositionWorld (REF:406-424, with getFootPositionBody REF:367-404):
  *       x_fb [B][12], q [B][10] joint angles  ->  pf_w [B][6]
