@@ -137,10 +137,39 @@ def duals_to_reference_order(lam):
                            lam[..., 32:36].reshape(lead + (4 * h,))], -1)
 
 
+# The evaluation family (`bmpc_evaluate`, `bmpc_evaluate_grad`, `bmpc_certify` and their _device twins): per operation the ctypes
+# output descriptor, the host and the device entry, whether the entries take `act_tol`, and the outputs in the order of the result
+# dict: (name, dtype, shape in terms of "B" and "h").  `BatchSolver._eval_host` / `_eval_device` do the work for every row.
+_EVAL_OPS = {
+    "evaluate": (_lib.CEvalOut, "bmpc_evaluate", "bmpc_evaluate_device", False,
+                 (("cost", "float64", ("B",)), ("objective", "float64", ("B",)), ("violation", "float64", ("B", 4)),
+                  ("states", "float64", ("B", "h", 13)))),
+    "evaluate_grad": (_lib.CGradOut, "bmpc_evaluate_grad", "bmpc_evaluate_grad_device", False,
+                      (("cost", "float64", ("B",)), ("grad_u", "float64", ("B", "h", 12)), ("grad_x0", "float64", ("B", 12)))),
+    "certify": (_lib.CCertOut, "bmpc_certify", "bmpc_certify_device", True,
+                (("lam", "float64", ("B", "h", 36)), ("resid", "float64", ("B", "h", 12)), ("summary", "float64", ("B", 4)),
+                 ("n_active", "int32", ("B",)), ("status", "int32", ("B",)))),
+}
+
+
+def _shape(spec, B, h):
+    return tuple({"B": B, "h": h}.get(d, d) for d in spec)
+
+
 def _ptr(a):
     """Address of a NumPy array as an integer (what a `c_void_p` parameter takes; building a ctypes pointer object per argument
     costs ~2 us each, fourteen of them per solve)."""
     return None if a is None else a.__array_interface__["data"][0]
+
+
+def _tensor_ptr(t, dtype, shape, dev):
+    """Device address of a tensor argument of the device-resident methods (None for None): it must be a contiguous `dtype` tensor
+    of `shape` on `dev` (ValueError)."""
+    if t is None:
+        return None
+    if t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+        raise ValueError(f"expected contiguous {dtype} tensor of shape {shape} on {dev}")
+    return t.data_ptr()
 
 
 class _HandleOwner:
@@ -300,19 +329,7 @@ class BatchSolver:
         fp32 values (widened exactly), so they pass through unchanged.  Its shape is checked before the call (ValueError).  An
         instance with a non-finite entry anywhere, or a reference pitch of +-90 degrees, gets NaN in all its outputs (reference
         values are therefore not checked here); no other instance is touched."""
-        c32 = _controls_f32(controls, self.h)
-        B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
-        if c32.shape[0] != B:
-            raise ValueError(f"controls must have shape ({B}, {self.h}, 12), got {c32.shape}")
-        x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h, finite=False)
-        if foot is None and foot_ref is None:
-            raise ValueError("foot is required unless foot_ref is given")
-        res = dict(cost=np.empty(B, np.float64), objective=np.empty(B, np.float64), violation=np.empty((B, 4), np.float64),
-                   states=np.empty((B, self.h, 13), np.float64) if want_states else None)
-        inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
-        eo = _lib.CEvalOut(_ptr(res["cost"]), _ptr(res["objective"]), _ptr(res["states"]), _ptr(res["violation"]))
-        _lib.check(self._lib.bmpc_evaluate(self._h, B, C.byref(inp), _ptr(c32), C.byref(eo)))
-        return res
+        return self._eval_host("evaluate", x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, skip=() if want_states else ("states",))
 
     def evaluate_grad(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None):
         """Gradient of `evaluate`'s cost (`bmpc_evaluate_grad`, include/bmpc.h): arguments as `evaluate` takes them.  Returns
@@ -321,18 +338,7 @@ class BatchSolver:
         they were supplied or generated (generated references depend on x_fb; that dependence is not differentiated).  The cost is
         an exact quadratic in the controls: `grad_u` at U + D minus `grad_u` at U is the Hessian times D.  Bad instances as in
         `evaluate`: NaN in all their outputs."""
-        c32 = _controls_f32(controls, self.h)
-        B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
-        if c32.shape[0] != B:
-            raise ValueError(f"controls must have shape ({B}, {self.h}, 12), got {c32.shape}")
-        x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h, finite=False)
-        if foot is None and foot_ref is None:
-            raise ValueError("foot is required unless foot_ref is given")
-        res = dict(cost=np.empty(B, np.float64), grad_u=np.empty((B, self.h, 12), np.float64), grad_x0=np.empty((B, 12), np.float64))
-        inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
-        go = _lib.CGradOut(_ptr(res["cost"]), _ptr(res["grad_u"]), _ptr(res["grad_x0"]))
-        _lib.check(self._lib.bmpc_evaluate_grad(self._h, B, C.byref(inp), _ptr(c32), C.byref(go)))
-        return res
+        return self._eval_host("evaluate_grad", x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref)
 
     def certify(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None, act_tol=ACT_TOL):
         """KKT certificate of GIVEN control sequences (`bmpc_certify`, include/bmpc.h): arguments as `evaluate_grad` takes them, and
@@ -343,6 +349,15 @@ class BatchSolver:
         violation (the maximum of `evaluate`'s four, same bits), complementarity = max |lam_i slack_i|, grad_scale = max |grad_u|
         (stationarity / grad_scale is the relative figure); n_active (B,) int32; status (B,) int32: 0 converged, 1 an iteration cap
         was reached (the residuals are valid, only not the smallest), 2 bad instance (NaN in the fp64 outputs, n_active -1)."""
+        res = self._eval_host("certify", x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, act_tol=act_tol)
+        for i, k in enumerate(("stationarity", "primal_ineq", "complementarity", "grad_scale")):
+            res[k] = res["summary"][:, i]
+        return res
+
+    def _eval_host(self, kind, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, act_tol=None, skip=()):
+        """The host entry of row `kind` of `_EVAL_OPS`: host arrays marshalled as `solve` does, outputs allocated (None for those
+        named in `skip`), one call.  Returns the dict of outputs."""
+        struct, entry, _, takes_tol, outputs = _EVAL_OPS[kind]
         c32 = _controls_f32(controls, self.h)
         B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
         if c32.shape[0] != B:
@@ -350,16 +365,15 @@ class BatchSolver:
         x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h, finite=False)
         if foot is None and foot_ref is None:
             raise ValueError("foot is required unless foot_ref is given")
-        act_tol = float(act_tol)
-        if act_tol != act_tol:
-            raise ValueError("act_tol must not be NaN")
-        res = dict(lam=np.empty((B, self.h, 36), np.float64), resid=np.empty((B, self.h, 12), np.float64),
-                   summary=np.empty((B, 4), np.float64), n_active=np.empty(B, np.int32), status=np.empty(B, np.int32))
+        tol = ()
+        if takes_tol:
+            tol = (float(act_tol),)
+            if tol[0] != tol[0]:
+                raise ValueError("act_tol must not be NaN")
+        res = {k: None if k in skip else np.empty(_shape(shp, B, self.h), dt) for k, dt, shp in outputs}
         inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
-        co = _lib.CCertOut(_ptr(res["lam"]), _ptr(res["resid"]), _ptr(res["summary"]), _ptr(res["n_active"]), _ptr(res["status"]))
-        _lib.check(self._lib.bmpc_certify(self._h, B, C.byref(inp), _ptr(c32), act_tol, C.byref(co)))
-        for i, k in enumerate(("stationarity", "primal_ineq", "complementarity", "grad_scale")):
-            res[k] = res["summary"][:, i]
+        out = struct(**{k: _ptr(v) for k, v in res.items()})
+        _lib.check(getattr(self._lib, entry)(self._h, B, C.byref(inp), _ptr(c32), *tol, C.byref(out)))
         return res
 
     def _io_views(self, B, with_x_cmd, with_mu, with_states):
@@ -464,37 +478,29 @@ class BatchSolver:
         B = x_fb.shape[0]
         h = self.h
         dev = x_fb.device
-
-        def chk(t, dtype, shape):
-            if t is None:
-                return 0
-            if t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError(f"expected contiguous {dtype} tensor of shape {shape} on {dev}")
-            return t.data_ptr()
-
         if dev.type != "cuda" or dev.index != self.device:
             raise ValueError(f"tensors must live on cuda:{self.device}")
         if controls is None:
             controls = torch.empty((B, h, 12), dtype=torch.float32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        inp = self._device_inputs(dev, B, x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref)
+        out = [_tensor_ptr(t, dtype, shape, dev) for t, dtype, shape in (
+            (controls, torch.float32, (B, h, 12)), (states, torch.float32, (B, h, 13)), (iters, torch.int32, (B,)),
+            (residuals, torch.float32, (B, 2)), (status, torch.int32, (B,)), (nfactor, torch.int32, (B,)))]
         if x_ref is not None or foot_ref is not None:
-            inp = _lib.CInputs(chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)) or None,
-                               chk(contact, torch.uint8, (B, h, 2)), chk(phase, torch.int32, (B,)),
-                               chk(x_cmd, torch.float32, (B, 12)) or None, chk(mu, torch.float32, (B, h, 2)) or None,
-                               chk(x_ref, torch.float32, (B, h, 12)) or None, chk(foot_ref, torch.float32, (B, h, 6)) or None)
-            _lib.check(self._lib.bmpc_solve_inputs_device(
-                self._h, B, C.byref(inp), chk(controls, torch.float32, (B, h, 12)), chk(states, torch.float32, (B, h, 13)) or None,
-                chk(iters, torch.int32, (B,)) or None, chk(residuals, torch.float32, (B, 2)) or None,
-                chk(status, torch.int32, (B,)) or None, chk(nfactor, torch.int32, (B,)) or None, st))
-            return controls, states
-        _lib.check(self._lib.bmpc_solve_batch_device(
-            self._h, B, chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)),
-            chk(contact, torch.uint8, (B, h, 2)), chk(phase, torch.int32, (B,)),
-            chk(x_cmd, torch.float32, (B, 12)) or None, chk(mu, torch.float32, (B, h, 2)) or None,
-            chk(controls, torch.float32, (B, h, 12)), chk(states, torch.float32, (B, h, 13)) or None,
-            chk(iters, torch.int32, (B,)) or None, chk(residuals, torch.float32, (B, 2)) or None,
-            chk(status, torch.int32, (B,)) or None, chk(nfactor, torch.int32, (B,)) or None, st))
+            _lib.check(self._lib.bmpc_solve_inputs_device(self._h, B, C.byref(_lib.CInputs(*inp)), *out, st))
+        else:
+            _lib.check(self._lib.bmpc_solve_batch_device(self._h, B, *inp[:6], *out, st))
         return controls, states
+
+    def _device_inputs(self, dev, B, x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref):
+        """The members of `bmpc_inputs` as device addresses, in its order (None: NULL), every tensor checked (`_tensor_ptr`)."""
+        import torch
+        h = self.h
+        return [_tensor_ptr(t, dtype, shape, dev) for t, dtype, shape in (
+            (x_fb, torch.float32, (B, 12)), (foot, torch.float32, (B, 6)), (contact, torch.uint8, (B, h, 2)), (phase, torch.int32, (B,)),
+            (x_cmd, torch.float32, (B, 12)), (mu, torch.float32, (B, h, 2)), (x_ref, torch.float32, (B, h, 12)),
+            (foot_ref, torch.float32, (B, h, 6)))]
 
     def evaluate_device(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None,
                         cost=None, objective=None, violation=None, states=None, want_states=False, stream=None):
@@ -503,35 +509,9 @@ class BatchSolver:
         synchronisation is needed in between.  Outputs are float64 tensors cost (B,), objective (B,), violation (B,4) and -- if
         passed, or with `want_states` -- states (B,h,13), allocated where not passed.  Asynchronous on `stream` (default: torch's
         current stream); nothing crosses PCIe.  Returns dict(cost, objective, violation, states | None)."""
-        import torch
-        B = x_fb.shape[0]
-        h = self.h
-        dev = x_fb.device
-
-        def chk(t, dtype, shape):
-            if t is None:
-                return None
-            if t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError(f"expected contiguous {dtype} tensor of shape {shape} on {dev}")
-            return t.data_ptr()
-
-        if dev.type != "cuda" or dev.index != self.device:
-            raise ValueError(f"tensors must live on cuda:{self.device}")
-        f64 = lambda shape: torch.empty(shape, dtype=torch.float64, device=dev)
-        cost = f64((B,)) if cost is None else cost
-        objective = f64((B,)) if objective is None else objective
-        violation = f64((B, 4)) if violation is None else violation
-        if states is None and want_states:
-            states = f64((B, h, 13))
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        inp = _lib.CInputs(chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)),
-                           chk(contact, torch.uint8, (B, h, 2)), chk(phase, torch.int32, (B,)),
-                           chk(x_cmd, torch.float32, (B, 12)), chk(mu, torch.float32, (B, h, 2)),
-                           chk(x_ref, torch.float32, (B, h, 12)), chk(foot_ref, torch.float32, (B, h, 6)))
-        eo = _lib.CEvalOut(chk(cost, torch.float64, (B,)), chk(objective, torch.float64, (B,)),
-                           chk(states, torch.float64, (B, h, 13)), chk(violation, torch.float64, (B, 4)))
-        _lib.check(self._lib.bmpc_evaluate_device(self._h, B, C.byref(inp), chk(controls, torch.float32, (B, h, 12)), C.byref(eo), st))
-        return dict(cost=cost, objective=objective, violation=violation, states=states)
+        return self._eval_device("evaluate", x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref,
+                                 dict(cost=cost, objective=objective, violation=violation, states=states),
+                                 skip=() if want_states else ("states",), stream=stream)
 
     def evaluate_grad_device(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None,
                              cost=None, grad_u=None, grad_x0=None, stream=None):
@@ -539,32 +519,8 @@ class BatchSolver:
         `evaluate_device` takes them.  Outputs are float64 tensors cost (B,), grad_u (B,h,12), grad_x0 (B,12), allocated where not
         passed.  Asynchronous on `stream` (default: torch's current stream); nothing crosses PCIe.  Returns dict(cost, grad_u,
         grad_x0)."""
-        import torch
-        B = x_fb.shape[0]
-        h = self.h
-        dev = x_fb.device
-
-        def chk(t, dtype, shape):
-            if t is None:
-                return None
-            if t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError(f"expected contiguous {dtype} tensor of shape {shape} on {dev}")
-            return t.data_ptr()
-
-        if dev.type != "cuda" or dev.index != self.device:
-            raise ValueError(f"tensors must live on cuda:{self.device}")
-        f64 = lambda shape: torch.empty(shape, dtype=torch.float64, device=dev)
-        cost = f64((B,)) if cost is None else cost
-        grad_u = f64((B, h, 12)) if grad_u is None else grad_u
-        grad_x0 = f64((B, 12)) if grad_x0 is None else grad_x0
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        inp = _lib.CInputs(chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)),
-                           chk(contact, torch.uint8, (B, h, 2)), chk(phase, torch.int32, (B,)),
-                           chk(x_cmd, torch.float32, (B, 12)), chk(mu, torch.float32, (B, h, 2)),
-                           chk(x_ref, torch.float32, (B, h, 12)), chk(foot_ref, torch.float32, (B, h, 6)))
-        go = _lib.CGradOut(chk(cost, torch.float64, (B,)), chk(grad_u, torch.float64, (B, h, 12)), chk(grad_x0, torch.float64, (B, 12)))
-        _lib.check(self._lib.bmpc_evaluate_grad_device(self._h, B, C.byref(inp), chk(controls, torch.float32, (B, h, 12)), C.byref(go), st))
-        return dict(cost=cost, grad_u=grad_u, grad_x0=grad_x0)
+        return self._eval_device("evaluate_grad", x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref,
+                                 dict(cost=cost, grad_u=grad_u, grad_x0=grad_x0), stream=stream)
 
     def certify_device(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None,
                        lam=None, resid=None, summary=None, n_active=None, status=None, act_tol=ACT_TOL, stream=None):
@@ -573,38 +529,38 @@ class BatchSolver:
         is needed in between.  Outputs are tensors lam (B,h,36), resid (B,h,12), summary (B,4) float64, n_active (B,), status (B,)
         int32, allocated where not passed.  Asynchronous on `stream` (default: torch's current stream); nothing crosses PCIe.
         Returns dict(lam, resid, summary, n_active, status)."""
+        return self._eval_device("certify", x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref,
+                                 dict(lam=lam, resid=resid, summary=summary, n_active=n_active, status=status), act_tol=act_tol,
+                                 stream=stream)
+
+    def _eval_device(self, kind, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, given, act_tol=None, skip=(),
+                     stream=None):
+        """The device entry of row `kind` of `_EVAL_OPS` on CUDA(HIP) torch tensors: `given` maps every output to the caller's
+        tensor or None (allocated here, unless named in `skip`: then it stays None).  Returns the dict of output tensors."""
         import torch
+        struct, _, entry, takes_tol, outputs = _EVAL_OPS[kind]
         B = x_fb.shape[0]
         h = self.h
         dev = x_fb.device
-
-        def chk(t, dtype, shape):
-            if t is None:
-                return None
-            if t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError(f"expected contiguous {dtype} tensor of shape {shape} on {dev}")
-            return t.data_ptr()
-
         if dev.type != "cuda" or dev.index != self.device:
             raise ValueError(f"tensors must live on cuda:{self.device}")
-        act_tol = float(act_tol)
-        if act_tol != act_tol:
-            raise ValueError("act_tol must not be NaN")
-        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
-        lam = new((B, h, 36), torch.float64) if lam is None else lam
-        resid = new((B, h, 12), torch.float64) if resid is None else resid
-        summary = new((B, 4), torch.float64) if summary is None else summary
-        n_active = new((B,), torch.int32) if n_active is None else n_active
-        status = new((B,), torch.int32) if status is None else status
+        tol = ()
+        if takes_tol:
+            tol = (float(act_tol),)
+            if tol[0] != tol[0]:
+                raise ValueError("act_tol must not be NaN")
+        res = {}
+        for k, dt, shp in outputs:
+            t = given[k]
+            if t is None and k not in skip:
+                t = torch.empty(_shape(shp, B, h), dtype=getattr(torch, dt), device=dev)
+            res[k] = t
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        inp = _lib.CInputs(chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)),
-                           chk(contact, torch.uint8, (B, h, 2)), chk(phase, torch.int32, (B,)),
-                           chk(x_cmd, torch.float32, (B, 12)), chk(mu, torch.float32, (B, h, 2)),
-                           chk(x_ref, torch.float32, (B, h, 12)), chk(foot_ref, torch.float32, (B, h, 6)))
-        co = _lib.CCertOut(chk(lam, torch.float64, (B, h, 36)), chk(resid, torch.float64, (B, h, 12)), chk(summary, torch.float64, (B, 4)),
-                           chk(n_active, torch.int32, (B,)), chk(status, torch.int32, (B,)))
-        _lib.check(self._lib.bmpc_certify_device(self._h, B, C.byref(inp), chk(controls, torch.float32, (B, h, 12)), act_tol, C.byref(co), st))
-        return dict(lam=lam, resid=resid, summary=summary, n_active=n_active, status=status)
+        inp = _lib.CInputs(*self._device_inputs(dev, B, x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref))
+        out = struct(**{k: _tensor_ptr(res[k], getattr(torch, dt), _shape(shp, B, h), dev) for k, dt, shp in outputs})
+        u = _tensor_ptr(controls, torch.float32, (B, h, 12), dev)
+        _lib.check(getattr(self._lib, entry)(self._h, B, C.byref(inp), u, *tol, C.byref(out), st))
+        return res
 
     def cost_torch(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None):
         """`evaluate`'s cost as a differentiable torch value: float64 tensor (B,) on the device, with gradients to `controls` (B,h,12)
@@ -721,14 +677,6 @@ class BatchSolver:
         B = x_fb.shape[0]
         if dev.type != "cuda" or dev.index != self.device:
             raise ValueError(f"tensors must live on cuda:{self.device}")
-
-        def chk(tn, dtype, shape):
-            if tn is None:
-                return None
-            if tn.device != dev or tn.dtype != dtype or not tn.is_contiguous() or tuple(tn.shape) != shape:
-                raise ValueError(f"expected contiguous {dtype} tensor of shape {shape} on {dev}")
-            return tn.data_ptr()
-
         gait = self._gait(period, offset, duty)
         u0 = torch.empty((steps, B, 12), dtype=torch.float32, device=dev)
         xt = torch.empty((steps, B, 12), dtype=torch.float32, device=dev)
@@ -736,10 +684,10 @@ class BatchSolver:
         st_any = torch.empty(B, dtype=torch.int32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
         _lib.check(self._lib.bmpc_rollout_device(
-            self._h, B, int(steps), chk(x_fb, torch.float32, (B, 12)), chk(foot, torch.float32, (B, 6)),
-            chk(t, torch.float64, (B,)), None if gait is None else C.byref(gait), chk(x_cmd, torch.float32, (B, 12)),
-            chk(mu, torch.float32, (B, self.h, 2)), u0.data_ptr(), xt.data_ptr(), None if its is None else its.data_ptr(),
-            st_any.data_ptr(), st))
+            self._h, B, int(steps), _tensor_ptr(x_fb, torch.float32, (B, 12), dev), _tensor_ptr(foot, torch.float32, (B, 6), dev),
+            _tensor_ptr(t, torch.float64, (B,), dev), None if gait is None else C.byref(gait),
+            _tensor_ptr(x_cmd, torch.float32, (B, 12), dev), _tensor_ptr(mu, torch.float32, (B, self.h, 2), dev),
+            u0.data_ptr(), xt.data_ptr(), None if its is None else its.data_ptr(), st_any.data_ptr(), st))
         return dict(u0=u0, x=xt, iters=its, status_any=st_any)
 
     def last_kernel_ms(self):
@@ -797,6 +745,44 @@ def close_cached_solvers():
     _SOLVERS.clear()
 
 
+def _batch_call(controls, t, mpc, biped, half, device, phase, x_ref, foot_ref, act_tol=0.0):
+    """What the `*_mpc_batch` wrappers of the evaluation family do before their call: the default `MPC`, `controls` as the
+    evaluation takes them, the references from the reference's orientation to the kernel layout, a NaN `act_tol` refused (the
+    certificate's; the others leave the default), the cached solver, the phase from `t`.  Every check comes before a solver handle
+    can be created.  Returns (solver, phase, x_ref, foot_ref, controls)."""
+    from .params import MPC
+    mpc = mpc if mpc is not None else MPC()
+    c32 = _controls_f32(controls, int(mpc.h))
+    xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
+    if float(act_tol) != float(act_tol):
+        raise ValueError("act_tol must not be NaN")
+    solver = _cached_solver(mpc, biped, half, device, None)
+    if phase is None:
+        phase = phase_indices(t, mpc.dt, mpc.h)
+    return solver, phase, xr, fr, c32
+
+
+def _contact_rows(contact, h):
+    """`contact` of a single-instance call as an array with at least h rows of 2 (ValueError otherwise)."""
+    contact = np.asarray(contact)
+    if contact.ndim != 2 or contact.shape[1] != 2 or contact.shape[0] < h:
+        raise ValueError(f"contact must have at least {h} rows of 2 (REF:239-249 indexes contact[k] for k < h)")
+    return contact
+
+
+def _batch_of_one(x_fb, t, foot, mpc, contact, controls, x_ref, foot_ref):
+    """One instance with `solve_mpc`'s arguments and `controls` (h,12) as a batch of one: the positional arguments of the
+    `*_mpc_batch` wrappers of the evaluation family and their reference keywords.  Shapes are checked here (ValueError)."""
+    h = int(mpc.h)
+    c = np.asarray(controls)
+    if c.shape != (h, 12):
+        raise ValueError(f"controls must have shape ({h}, 12), got {c.shape}")
+    contact = _contact_rows(contact, h)
+    args = (np.asarray(x_fb, float).reshape(1, 12), [t], np.asarray(foot, float).reshape(1, 6), contact[None, :h, :], c[None])
+    refs = dict(x_ref=None if x_ref is None else np.asarray(x_ref)[None], foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None])
+    return args, refs
+
+
 def solve_mpc_batch(x_fb, t, foot, contact, mpc=None, biped=None, x_cmd=None, mu=None, phase=None, half=None,
                     device=0, solver_options=None, return_info=False, x_ref=None, foot_ref=None):
     """B instances of REF:187 `solve_mpc`.  x_fb (B,12), t (B,) seconds [or phase (B,) directly],
@@ -823,9 +809,7 @@ def solve_mpc(x_fb, t, foot, mpc, biped, contact, half=None, device=0, solver_op
     `controls (h,12)`), inputs not mutated, silent.  `x_ref` (13,h) / `foot_ref` (6,h): what the solve tracks in place of
     REF:61-70 / REF:72-109 -- e.g. `get_reference_trajectory(...)` edited (stairs, a crouch, a planner's footholds)."""
     h = int(mpc.h)
-    contact = np.asarray(contact)
-    if contact.ndim != 2 or contact.shape[1] != 2 or contact.shape[0] < h:
-        raise ValueError(f"contact must have at least {h} rows of 2 (REF:239-249 indexes contact[k] for k < h)")
+    contact = _contact_rows(contact, h)
     x_fb = np.asarray(x_fb, float).reshape(12)
     foot = np.asarray(foot, float).reshape(6)
     states, controls = solve_mpc_batch(x_fb[None], [t], foot[None], contact[None, :h, :], mpc=mpc, biped=biped,
@@ -840,30 +824,15 @@ def evaluate_mpc_batch(x_fb, t, foot, contact, controls, mpc=None, biped=None, x
     """What the model of REF:187-304 makes of given control sequences: `solve_mpc_batch`'s call surface (references in the
     reference's orientation, the cached handle per horizon and device) with `controls` (B,h,12) added.  Returns
     dict(cost (B,), objective (B,), violation (B,4), states (B,h,13)) as `BatchSolver.evaluate`."""
-    from .params import MPC
-    mpc = mpc if mpc is not None else MPC()
-    c32 = _controls_f32(controls, int(mpc.h))
-    xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
-    solver = _cached_solver(mpc, biped, half, device, None)
-    if phase is None:
-        phase = phase_indices(t, mpc.dt, mpc.h)
+    solver, phase, xr, fr, c32 = _batch_call(controls, t, mpc, biped, half, device, phase, x_ref, foot_ref)
     return solver.evaluate(x_fb, foot, contact, phase, c32, x_cmd=x_cmd, mu=mu, x_ref=xr, foot_ref=fr, want_states=True)
 
 
 def evaluate_mpc(x_fb, t, foot, mpc, biped, contact, controls, half=None, device=0, x_ref=None, foot_ref=None):
     """`evaluate_mpc_batch` for one instance with `solve_mpc`'s arguments and `controls` (h,12) -- e.g. what `solve_mpc` returned.
     Returns dict(cost float, objective float, violation (4,), states (h,13))."""
-    h = int(mpc.h)
-    c = np.asarray(controls)
-    if c.shape != (h, 12):
-        raise ValueError(f"controls must have shape ({h}, 12), got {c.shape}")
-    contact = np.asarray(contact)
-    if contact.ndim != 2 or contact.shape[1] != 2 or contact.shape[0] < h:
-        raise ValueError(f"contact must have at least {h} rows of 2 (REF:239-249 indexes contact[k] for k < h)")
-    r = evaluate_mpc_batch(np.asarray(x_fb, float).reshape(1, 12), [t], np.asarray(foot, float).reshape(1, 6), contact[None, :h, :],
-                           c[None], mpc=mpc, biped=biped, half=half, device=device,
-                           x_ref=None if x_ref is None else np.asarray(x_ref)[None],
-                           foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None])
+    args, refs = _batch_of_one(x_fb, t, foot, mpc, contact, controls, x_ref, foot_ref)
+    r = evaluate_mpc_batch(*args, mpc=mpc, biped=biped, half=half, device=device, **refs)
     return dict(cost=float(r["cost"][0]), objective=float(r["objective"][0]), violation=r["violation"][0], states=r["states"][0])
 
 
@@ -871,30 +840,15 @@ def evaluate_grad_mpc_batch(x_fb, t, foot, contact, controls, mpc=None, biped=No
                             device=0, x_ref=None, foot_ref=None):
     """Gradient of the cost `evaluate_mpc_batch` returns: the same call surface (references in the reference's orientation, the
     cached handle per horizon and device).  Returns dict(cost (B,), grad_u (B,h,12), grad_x0 (B,12)) as `BatchSolver.evaluate_grad`."""
-    from .params import MPC
-    mpc = mpc if mpc is not None else MPC()
-    c32 = _controls_f32(controls, int(mpc.h))
-    xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
-    solver = _cached_solver(mpc, biped, half, device, None)
-    if phase is None:
-        phase = phase_indices(t, mpc.dt, mpc.h)
+    solver, phase, xr, fr, c32 = _batch_call(controls, t, mpc, biped, half, device, phase, x_ref, foot_ref)
     return solver.evaluate_grad(x_fb, foot, contact, phase, c32, x_cmd=x_cmd, mu=mu, x_ref=xr, foot_ref=fr)
 
 
 def evaluate_grad_mpc(x_fb, t, foot, mpc, biped, contact, controls, half=None, device=0, x_ref=None, foot_ref=None):
     """`evaluate_grad_mpc_batch` for one instance with `evaluate_mpc`'s arguments.  Returns dict(cost float, grad_u (h,12),
     grad_x0 (12,))."""
-    h = int(mpc.h)
-    c = np.asarray(controls)
-    if c.shape != (h, 12):
-        raise ValueError(f"controls must have shape ({h}, 12), got {c.shape}")
-    contact = np.asarray(contact)
-    if contact.ndim != 2 or contact.shape[1] != 2 or contact.shape[0] < h:
-        raise ValueError(f"contact must have at least {h} rows of 2 (REF:239-249 indexes contact[k] for k < h)")
-    r = evaluate_grad_mpc_batch(np.asarray(x_fb, float).reshape(1, 12), [t], np.asarray(foot, float).reshape(1, 6),
-                                contact[None, :h, :], c[None], mpc=mpc, biped=biped, half=half, device=device,
-                                x_ref=None if x_ref is None else np.asarray(x_ref)[None],
-                                foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None])
+    args, refs = _batch_of_one(x_fb, t, foot, mpc, contact, controls, x_ref, foot_ref)
+    r = evaluate_grad_mpc_batch(*args, mpc=mpc, biped=biped, half=half, device=device, **refs)
     return dict(cost=float(r["cost"][0]), grad_u=r["grad_u"][0], grad_x0=r["grad_x0"][0])
 
 
@@ -902,32 +856,15 @@ def certify_mpc_batch(x_fb, t, foot, contact, controls, mpc=None, biped=None, x_
                       device=0, x_ref=None, foot_ref=None, act_tol=ACT_TOL):
     """KKT certificate of given control sequences: `evaluate_grad_mpc_batch`'s call surface (references in the reference's
     orientation, the cached handle per horizon and device) plus `act_tol`.  Returns the dict of `BatchSolver.certify`."""
-    from .params import MPC
-    mpc = mpc if mpc is not None else MPC()
-    c32 = _controls_f32(controls, int(mpc.h))
-    xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
-    if float(act_tol) != float(act_tol):
-        raise ValueError("act_tol must not be NaN")
-    solver = _cached_solver(mpc, biped, half, device, None)
-    if phase is None:
-        phase = phase_indices(t, mpc.dt, mpc.h)
+    solver, phase, xr, fr, c32 = _batch_call(controls, t, mpc, biped, half, device, phase, x_ref, foot_ref, act_tol)
     return solver.certify(x_fb, foot, contact, phase, c32, x_cmd=x_cmd, mu=mu, x_ref=xr, foot_ref=fr, act_tol=act_tol)
 
 
 def certify_mpc(x_fb, t, foot, mpc, biped, contact, controls, half=None, device=0, x_ref=None, foot_ref=None, act_tol=ACT_TOL):
     """`certify_mpc_batch` for one instance with `evaluate_mpc`'s arguments -- e.g. on what `solve_mpc` returned.  Returns
     dict(lam (h,36), resid (h,12), summary (4,), stationarity, primal_ineq, complementarity, grad_scale floats, n_active, status ints)."""
-    h = int(mpc.h)
-    c = np.asarray(controls)
-    if c.shape != (h, 12):
-        raise ValueError(f"controls must have shape ({h}, 12), got {c.shape}")
-    contact = np.asarray(contact)
-    if contact.ndim != 2 or contact.shape[1] != 2 or contact.shape[0] < h:
-        raise ValueError(f"contact must have at least {h} rows of 2 (REF:239-249 indexes contact[k] for k < h)")
-    r = certify_mpc_batch(np.asarray(x_fb, float).reshape(1, 12), [t], np.asarray(foot, float).reshape(1, 6), contact[None, :h, :],
-                          c[None], mpc=mpc, biped=biped, half=half, device=device,
-                          x_ref=None if x_ref is None else np.asarray(x_ref)[None],
-                          foot_ref=None if foot_ref is None else np.asarray(foot_ref)[None], act_tol=act_tol)
+    args, refs = _batch_of_one(x_fb, t, foot, mpc, contact, controls, x_ref, foot_ref)
+    r = certify_mpc_batch(*args, mpc=mpc, biped=biped, half=half, device=device, **refs, act_tol=act_tol)
     out = dict(lam=r["lam"][0], resid=r["resid"][0], summary=r["summary"][0], n_active=int(r["n_active"][0]), status=int(r["status"][0]))
     for k in ("stationarity", "primal_ineq", "complementarity", "grad_scale"):
         out[k] = float(r[k][0])

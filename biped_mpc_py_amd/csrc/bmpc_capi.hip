@@ -662,6 +662,143 @@ int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const
   return BMPC_OK;
 }
 
+// Host inputs onto the device, queued on the handle's own stream: staged through the handle's scratch arrays (the synchronous
+// host entries of the evaluation family and bmpc_debug_assemble_inputs).  `controls`: host controls to stage with them, or null
+// (the scratch array is sized either way: the assembly launch stores there).  `din`: the descriptor of the copies.
+int stage_inputs(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, bmpc_inputs* din) {
+  const size_t n = (size_t)B, H = (size_t)h->dev.h;
+  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->contact.ensure(n * H * 2));
+  HIP_TRY(h->phase.ensure(n)); HIP_TRY(h->controls.ensure(n * H * 12));
+  if (in.foot) HIP_TRY(h->foot.ensure(n * 6));
+  if (in.x_cmd) HIP_TRY(h->x_cmd.ensure(n * 12));
+  if (in.mu) HIP_TRY(h->mu.ensure(n * H * 2));
+  if (in.x_ref) HIP_TRY(h->x_ref.ensure(n * H * 12));
+  if (in.foot_ref) HIP_TRY(h->foot_ref.ensure(n * H * 6));
+  hipStream_t st = h->stream;
+  HIP_TRY(hipMemcpyAsync(h->x_fb.p, in.x_fb, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in.foot) HIP_TRY(hipMemcpyAsync(h->foot.p, in.foot, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->contact.p, in.contact, n * H * 2, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->phase.p, in.phase, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (controls) HIP_TRY(hipMemcpyAsync(h->controls.p, controls, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in.x_cmd) HIP_TRY(hipMemcpyAsync(h->x_cmd.p, in.x_cmd, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in.mu) HIP_TRY(hipMemcpyAsync(h->mu.p, in.mu, n * H * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in.x_ref) HIP_TRY(hipMemcpyAsync(h->x_ref.p, in.x_ref, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (in.foot_ref) HIP_TRY(hipMemcpyAsync(h->foot_ref.p, in.foot_ref, n * H * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+  *din = {h->x_fb.p, in.foot ? h->foot.p : nullptr, h->contact.p, h->phase.p, in.x_cmd ? h->x_cmd.p : nullptr,
+          in.mu ? h->mu.p : nullptr, in.x_ref ? h->x_ref.p : nullptr, in.foot_ref ? h->foot_ref.p : nullptr};
+  return BMPC_OK;
+}
+
+// ---- the evaluation family: bmpc_evaluate, bmpc_evaluate_grad, bmpc_certify and their _device twins.  One launch each, nothing
+// of the handle's per-solve state involved.  The kernels differ (bmpc_evaluate.hip, bmpc_evaluate_grad.hip, bmpc_certify.hip);
+// the path around them is stated once here.  A further operation is a kernel, an EvalOp row, a slot table and two entries.
+
+// one member of an operation's output descriptor: the caller's pointer (null: not wanted), elements per instance
+// (fixed + per_step * h) and bytes per element
+struct OutSlot { void* p; size_t fixed, per_step, elem; };
+template <size_t N> struct OutSlots { OutSlot s[N]; };
+
+// `launch`: the operation's kernel on device-addressable inputs; `out`: one pointer per slot, in the table's order
+using EvalLaunch = int (*)(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, double act_tol, void* const* out,
+                           hipStream_t st);
+struct EvalOp { const char *null_out, *none_out; EvalLaunch launch; };
+
+template <auto Kernel, typename... Tail>
+int launch_eval(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, hipStream_t st, Tail... tail) {
+  const long long lanes = (long long)B * bmpc::eval_lanes(h->params.h);
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)((lanes + bmpc::EVAL_NT - 1) / bmpc::EVAL_NT)), dim3(bmpc::EVAL_NT), 0, st,
+                     bmpc::eval_params(h->params, h->dev.Iinv), B, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd, in.mu, in.x_ref,
+                     in.foot_ref, controls, tail...);
+  HIP_TRY(hipGetLastError());
+  return BMPC_OK;
+}
+
+int launch_evaluate(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, double, void* const* o, hipStream_t st) {
+  return launch_eval<bmpc::evaluate_kernel>(h, B, in, controls, st, bmpc::EvalOut{(double*)o[0], (double*)o[1], (double*)o[2], (double*)o[3]});
+}
+int launch_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, double, void* const* o, hipStream_t st) {
+  return launch_eval<bmpc::evaluate_grad_kernel>(h, B, in, controls, st, bmpc::GradOut{(double*)o[0], (double*)o[1], (double*)o[2]});
+}
+int launch_certify(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, double act_tol, void* const* o, hipStream_t st) {
+  return launch_eval<bmpc::certify_kernel>(h, B, in, controls, st, act_tol,
+                                           bmpc::CertOut{(double*)o[0], (double*)o[1], (double*)o[2], (int32_t*)o[3], (int32_t*)o[4]});
+}
+
+const EvalOp EVALUATE = {"null bmpc_eval_out", "bmpc_eval_out: at least one of cost, objective, states, violation must be non-null",
+                         launch_evaluate};
+const EvalOp EVALUATE_GRAD = {"null bmpc_grad_out", "bmpc_grad_out: at least one of cost, grad_u, grad_x0 must be non-null",
+                              launch_evaluate_grad};
+const EvalOp CERTIFY = {"null bmpc_cert_out", "bmpc_cert_out: at least one of lam, resid, summary, n_active, status must be non-null",
+                        launch_certify};
+
+// the slot tables, in the member order of the descriptors (include/bmpc.h); a null descriptor gives all-null slots
+OutSlots<4> slots_of(const bmpc_eval_out* out) {
+  const bmpc_eval_out o = out ? *out : bmpc_eval_out{};
+  return {{{o.cost, 1, 0, 8}, {o.objective, 1, 0, 8}, {o.states, 0, 13, 8}, {o.violation, 4, 0, 8}}};
+}
+OutSlots<3> slots_of(const bmpc_grad_out* out) {
+  const bmpc_grad_out o = out ? *out : bmpc_grad_out{};
+  return {{{o.cost, 1, 0, 8}, {o.grad_u, 0, 12, 8}, {o.grad_x0, 12, 0, 8}}};
+}
+OutSlots<5> slots_of(const bmpc_cert_out* out) {
+  const bmpc_cert_out o = out ? *out : bmpc_cert_out{};
+  return {{{o.lam, 0, 36, 8}, {o.resid, 0, 12, 8}, {o.summary, 4, 0, 8}, {o.n_active, 1, 0, 4}, {o.status, 1, 0, 4}}};
+}
+
+// what every entry checks before a device is touched (and before the handle is read): an error code (< 0), BMPC_OK when there is
+// nothing to do, 1 to go on.  `out`: the entry's output descriptor
+template <size_t N>
+int check_eval(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const void* out,
+               const OutSlots<N>& slots) {
+  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
+  if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
+  if (!controls) return fail(BMPC_ERR_INVALID, "null controls");
+  if (!out) return fail(BMPC_ERR_INVALID, op.null_out);
+  bool any_out = false;
+  for (const OutSlot& s : slots.s) any_out = any_out || s.p;
+  if (!any_out) return fail(BMPC_ERR_INVALID, op.none_out);
+  return check_common(h, B, in->x_fb, in->foot, in->contact, in->phase, controls, in->foot_ref);
+}
+
+// the device entry: everything device-addressable, asynchronous on `stream`
+template <size_t N>
+int eval_device(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol,
+                const void* out, const OutSlots<N>& slots, void* stream) {
+  if (int rc = check_eval(op, h, B, in, controls, out, slots); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  void* d[N];
+  for (size_t i = 0; i < N; ++i) d[i] = slots.s[i].p;
+  return op.launch(h, B, *in, controls, act_tol, d, pick_stream(h, stream));
+}
+
+// the host entry: the wanted outputs are carved out of the handle's eval_out block (each on an 8-byte boundary), the inputs
+// staged, the kernel launched on the copies, the outputs copied back; synchronous on the handle's own stream
+template <size_t N>
+int eval_host(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol,
+              const void* out, const OutSlots<N>& slots) {
+  if (int rc = check_eval(op, h, B, in, controls, out, slots); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t n = (size_t)B, H = (size_t)h->dev.h;
+  size_t bytes[N], off[N], tot = 0;                       // off, tot in doubles
+  for (size_t i = 0; i < N; ++i) {
+    const OutSlot& s = slots.s[i];
+    bytes[i] = s.p ? n * (s.fixed + s.per_step * H) * s.elem : 0;
+    off[i] = tot;
+    tot += (bytes[i] + sizeof(double) - 1) / sizeof(double);
+  }
+  HIP_TRY(h->eval_out.ensure(tot));
+  bmpc_inputs din;
+  if (int rc = stage_inputs(h, B, *in, controls, &din); rc != BMPC_OK) return rc;
+  hipStream_t st = h->stream;
+  void* d[N];
+  for (size_t i = 0; i < N; ++i) d[i] = slots.s[i].p ? h->eval_out.p + off[i] : nullptr;
+  if (int rc = op.launch(h, B, din, h->controls.p, act_tol, d, st); rc != BMPC_OK) return rc;
+  for (size_t i = 0; i < N; ++i)
+    if (slots.s[i].p) HIP_TRY(hipMemcpyAsync(slots.s[i].p, d[i], bytes[i], hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return BMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -991,20 +1128,10 @@ int bmpc_debug_assemble_inputs(bmpc_handle h, int B, const bmpc_inputs* in, doub
                                double* qt) {
   if (!h) return fail(BMPC_ERR_INVALID, "null handle");
   if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
-  const float *x_fb = in->x_fb, *foot = in->foot, *x_cmd = in->x_cmd, *mu = in->mu, *xr_in = in->x_ref, *fr_in = in->foot_ref;
-  const uint8_t* contact = in->contact;
-  const int32_t* phase = in->phase;
   float dummy = 0;
-  if (int rc = check_common(h, B, x_fb, foot, contact, phase, &dummy, fr_in); rc <= 0) return rc;
+  if (int rc = check_common(h, B, in->x_fb, in->foot, in->contact, in->phase, &dummy, in->foot_ref); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B, H = (size_t)h->dev.h, NW = 6 * H;
-  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->contact.ensure(n * H * 2));
-  HIP_TRY(h->phase.ensure(n)); HIP_TRY(h->controls.ensure(n * H * 12));
-  if (foot) HIP_TRY(h->foot.ensure(n * 6));
-  if (x_cmd) HIP_TRY(h->x_cmd.ensure(n * 12));
-  if (mu) HIP_TRY(h->mu.ensure(n * H * 2));
-  if (xr_in) HIP_TRY(h->x_ref.ensure(n * H * 12));
-  if (fr_in) HIP_TRY(h->foot_ref.ensure(n * H * 6));
   // only what the caller asked for is formed: Gt alone is n (6h)^2 doubles (1.9 GB at B = 4096, h = 40), and the Gt / qt
   // views exist on the dense family only (h <= 20) -- a caller that wants the references gets them at every horizon
   if ((Gt || qt) && !dense_horizon(h->dev.h))
@@ -1014,22 +1141,12 @@ int bmpc_debug_assemble_inputs(bmpc_handle h, int B, const bmpc_inputs* in, doub
   HIP_TRY(h->dbg.ensure(tot));
   hipStream_t st = h->stream;
   HIP_TRY(hipMemsetAsync(h->dbg.p, 0, tot * sizeof(double), st));
-  HIP_TRY(hipMemcpyAsync(h->x_fb.p, x_fb, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (foot) HIP_TRY(hipMemcpyAsync(h->foot.p, foot, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->contact.p, contact, n * H * 2, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->phase.p, phase, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  if (x_cmd) HIP_TRY(hipMemcpyAsync(h->x_cmd.p, x_cmd, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (mu) HIP_TRY(hipMemcpyAsync(h->mu.p, mu, n * H * 2 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (xr_in) HIP_TRY(hipMemcpyAsync(h->x_ref.p, xr_in, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (fr_in) HIP_TRY(hipMemcpyAsync(h->foot_ref.p, fr_in, n * H * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+  bmpc_inputs din;
+  if (int rc = stage_inputs(h, B, *in, nullptr, &din); rc != BMPC_OK) return rc;
   bmpc::DebugOut dbg = {h->dbg.p + o_xr, h->dbg.p + o_fr, Gt ? h->dbg.p + o_gt : nullptr, qt ? h->dbg.p + o_qt : nullptr, nullptr, 1};
   SolveIO io;
-  io.x_fb = h->x_fb.p; io.contact = h->contact.p; io.phase = h->phase.p; io.controls = h->controls.p;
-  if (foot) io.foot = h->foot.p;
-  if (x_cmd) io.x_cmd = h->x_cmd.p;
-  if (mu) io.mu = h->mu.p;
-  if (xr_in) io.x_ref = h->x_ref.p;
-  if (fr_in) io.foot_ref = h->foot_ref.p;
+  io.x_fb = din.x_fb; io.foot = din.foot; io.contact = din.contact; io.phase = din.phase; io.x_cmd = din.x_cmd; io.mu = din.mu;
+  io.x_ref = din.x_ref; io.foot_ref = din.foot_ref; io.controls = h->controls.p;
   if (int rc = launch(h, B, io, dbg, st, nullptr); rc != BMPC_OK) return rc;
   if (x_ref) HIP_TRY(hipMemcpyAsync(x_ref, h->dbg.p + o_xr, n * H * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
   if (foot_ref) HIP_TRY(hipMemcpyAsync(foot_ref, h->dbg.p + o_fr, n * H * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1046,185 +1163,33 @@ int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* fo
   return bmpc_debug_assemble_inputs(h, B, &in, x_ref, foot_ref, Gt, qt);
 }
 
-// ---- evaluation of given controls (bmpc_evaluate.hip): one launch, nothing of the handle's per-solve state involved
-
-// what every entry checks before a device is touched: an error code (< 0), BMPC_OK when there is nothing to do, 1 to go on.
-// `out`: the entry's output descriptor, `any_out`: whether one of its members is non-null, `null_out` / `none_out`: the messages
-static int check_evaluate_args(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const void* out, bool any_out,
-                               const char* null_out, const char* none_out) {
-  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
-  if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
-  if (!controls) return fail(BMPC_ERR_INVALID, "null controls");
-  if (!out) return fail(BMPC_ERR_INVALID, null_out);
-  if (!any_out) return fail(BMPC_ERR_INVALID, none_out);
-  return check_common(h, B, in->x_fb, in->foot, in->contact, in->phase, controls, in->foot_ref);
-}
-
-static int check_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out) {
-  return check_evaluate_args(h, B, in, controls, out, out && (out->cost || out->objective || out->states || out->violation),
-                             "null bmpc_eval_out", "bmpc_eval_out: at least one of cost, objective, states, violation must be non-null");
-}
-
-static int check_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_grad_out* out) {
-  return check_evaluate_args(h, B, in, controls, out, out && (out->cost || out->grad_u || out->grad_x0),
-                             "null bmpc_grad_out", "bmpc_grad_out: at least one of cost, grad_u, grad_x0 must be non-null");
-}
-
-static dim3 evaluate_grid(bmpc_handle h, int B) {
-  const int hh = h->params.h;
-  const int L = hh <= 16 ? 16 : (hh <= 32 ? 32 : 64);          // lanes per instance (bmpc_evaluate.hip)
-  const long long lanes = (long long)B * L;
-  return dim3((unsigned)((lanes + bmpc::EVAL_NT - 1) / bmpc::EVAL_NT));
-}
-
-static int launch_evaluate(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const bmpc_eval_out& out, hipStream_t st) {
-  const bmpc::EvalOut o = {out.cost, out.objective, out.states, out.violation};
-  hipLaunchKernelGGL(bmpc::evaluate_kernel, evaluate_grid(h, B), dim3(bmpc::EVAL_NT), 0, st,
-                     bmpc::eval_params(h->params, h->dev.Iinv), B, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd, in.mu, in.x_ref,
-                     in.foot_ref, controls, o);
-  HIP_TRY(hipGetLastError());
-  return BMPC_OK;
-}
-
-static int launch_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const bmpc_grad_out& out,
-                                hipStream_t st) {
-  const bmpc::GradOut o = {out.cost, out.grad_u, out.grad_x0};
-  hipLaunchKernelGGL(bmpc::evaluate_grad_kernel, evaluate_grid(h, B), dim3(bmpc::EVAL_NT), 0, st,
-                     bmpc::eval_params(h->params, h->dev.Iinv), B, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd, in.mu, in.x_ref,
-                     in.foot_ref, controls, o);
-  HIP_TRY(hipGetLastError());
-  return BMPC_OK;
-}
-
-// host inputs of an evaluation onto the device, queued on the handle's own stream: staged through the scratch arrays of
-// bmpc_debug_assemble (synchronous calls on that stream, like the host entries here).  `din`: the descriptor of the copies
-static int stage_evaluate_inputs(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, bmpc_inputs* din) {
-  const size_t n = (size_t)B, H = (size_t)h->dev.h;
-  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->contact.ensure(n * H * 2));
-  HIP_TRY(h->phase.ensure(n)); HIP_TRY(h->controls.ensure(n * H * 12));
-  if (in->foot) HIP_TRY(h->foot.ensure(n * 6));
-  if (in->x_cmd) HIP_TRY(h->x_cmd.ensure(n * 12));
-  if (in->mu) HIP_TRY(h->mu.ensure(n * H * 2));
-  if (in->x_ref) HIP_TRY(h->x_ref.ensure(n * H * 12));
-  if (in->foot_ref) HIP_TRY(h->foot_ref.ensure(n * H * 6));
-  hipStream_t st = h->stream;
-  HIP_TRY(hipMemcpyAsync(h->x_fb.p, in->x_fb, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in->foot) HIP_TRY(hipMemcpyAsync(h->foot.p, in->foot, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->contact.p, in->contact, n * H * 2, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->phase.p, in->phase, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->controls.p, controls, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in->x_cmd) HIP_TRY(hipMemcpyAsync(h->x_cmd.p, in->x_cmd, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in->mu) HIP_TRY(hipMemcpyAsync(h->mu.p, in->mu, n * H * 2 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in->x_ref) HIP_TRY(hipMemcpyAsync(h->x_ref.p, in->x_ref, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in->foot_ref) HIP_TRY(hipMemcpyAsync(h->foot_ref.p, in->foot_ref, n * H * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-  *din = {h->x_fb.p, in->foot ? h->foot.p : nullptr, h->contact.p, h->phase.p, in->x_cmd ? h->x_cmd.p : nullptr,
-          in->mu ? h->mu.p : nullptr, in->x_ref ? h->x_ref.p : nullptr, in->foot_ref ? h->foot_ref.p : nullptr};
-  return BMPC_OK;
-}
+// ---- the evaluation family (helpers above): evaluation of given controls, the gradient of its cost, the KKT certificate
 
 int bmpc_evaluate_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out, void* stream) {
-  if (int rc = check_evaluate(h, B, in, controls, out); rc <= 0) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  return launch_evaluate(h, B, *in, controls, *out, pick_stream(h, stream));
+  return eval_device(EVALUATE, h, B, in, controls, 0.0, out, slots_of(out), stream);
 }
 
 int bmpc_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out) {
-  if (int rc = check_evaluate(h, B, in, controls, out); rc <= 0) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B, H = (size_t)h->dev.h;
-  const size_t o_c = 0, o_o = o_c + (out->cost ? n : 0), o_v = o_o + (out->objective ? n : 0), o_s = o_v + (out->violation ? n * 4 : 0),
-               tot = o_s + (out->states ? n * H * 13 : 0);
-  HIP_TRY(h->eval_out.ensure(tot));
-  bmpc_inputs din;
-  if (int rc = stage_evaluate_inputs(h, B, in, controls, &din); rc != BMPC_OK) return rc;
-  hipStream_t st = h->stream;
-  double* d = h->eval_out.p;
-  const bmpc_eval_out dout = {out->cost ? d + o_c : nullptr, out->objective ? d + o_o : nullptr, out->states ? d + o_s : nullptr,
-                              out->violation ? d + o_v : nullptr};
-  if (int rc = launch_evaluate(h, B, din, h->controls.p, dout, st); rc != BMPC_OK) return rc;
-  if (out->cost) HIP_TRY(hipMemcpyAsync(out->cost, dout.cost, n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (out->objective) HIP_TRY(hipMemcpyAsync(out->objective, dout.objective, n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (out->violation) HIP_TRY(hipMemcpyAsync(out->violation, dout.violation, n * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (out->states) HIP_TRY(hipMemcpyAsync(out->states, dout.states, n * H * 13 * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return BMPC_OK;
+  return eval_host(EVALUATE, h, B, in, controls, 0.0, out, slots_of(out));
 }
 
-// ---- gradient of the evaluated cost (bmpc_evaluate_grad.hip): the entries of the evaluation with other outputs
-
 int bmpc_evaluate_grad_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_grad_out* out, void* stream) {
-  if (int rc = check_evaluate_grad(h, B, in, controls, out); rc <= 0) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  return launch_evaluate_grad(h, B, *in, controls, *out, pick_stream(h, stream));
+  return eval_device(EVALUATE_GRAD, h, B, in, controls, 0.0, out, slots_of(out), stream);
 }
 
 int bmpc_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_grad_out* out) {
-  if (int rc = check_evaluate_grad(h, B, in, controls, out); rc <= 0) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B, H = (size_t)h->dev.h;
-  const size_t o_c = 0, o_x = o_c + (out->cost ? n : 0), o_u = o_x + (out->grad_x0 ? n * 12 : 0), tot = o_u + (out->grad_u ? n * H * 12 : 0);
-  HIP_TRY(h->eval_out.ensure(tot));
-  bmpc_inputs din;
-  if (int rc = stage_evaluate_inputs(h, B, in, controls, &din); rc != BMPC_OK) return rc;
-  hipStream_t st = h->stream;
-  double* d = h->eval_out.p;
-  const bmpc_grad_out dout = {out->cost ? d + o_c : nullptr, out->grad_u ? d + o_u : nullptr, out->grad_x0 ? d + o_x : nullptr};
-  if (int rc = launch_evaluate_grad(h, B, din, h->controls.p, dout, st); rc != BMPC_OK) return rc;
-  if (out->cost) HIP_TRY(hipMemcpyAsync(out->cost, dout.cost, n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (out->grad_x0) HIP_TRY(hipMemcpyAsync(out->grad_x0, dout.grad_x0, n * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (out->grad_u) HIP_TRY(hipMemcpyAsync(out->grad_u, dout.grad_u, n * H * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return BMPC_OK;
-}
-
-// ---- KKT certificate of given controls (bmpc_certify.hip): the entries of the evaluation with an activity tolerance and other outputs
-
-static int check_certify(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol, const bmpc_cert_out* out) {
-  if (act_tol != act_tol) return fail(BMPC_ERR_INVALID, "act_tol is NaN");
-  return check_evaluate_args(h, B, in, controls, out, out && (out->lam || out->resid || out->summary || out->n_active || out->status),
-                             "null bmpc_cert_out", "bmpc_cert_out: at least one of lam, resid, summary, n_active, status must be non-null");
-}
-
-static int launch_certify(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, double act_tol, const bmpc_cert_out& out,
-                          hipStream_t st) {
-  const bmpc::CertOut o = {out.lam, out.resid, out.summary, out.n_active, out.status};
-  hipLaunchKernelGGL(bmpc::certify_kernel, evaluate_grid(h, B), dim3(bmpc::EVAL_NT), 0, st,
-                     bmpc::eval_params(h->params, h->dev.Iinv), B, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd, in.mu, in.x_ref,
-                     in.foot_ref, controls, act_tol, o);
-  HIP_TRY(hipGetLastError());
-  return BMPC_OK;
+  return eval_host(EVALUATE_GRAD, h, B, in, controls, 0.0, out, slots_of(out));
 }
 
 int bmpc_certify_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol, const bmpc_cert_out* out,
                         void* stream) {
-  if (int rc = check_certify(h, B, in, controls, act_tol, out); rc <= 0) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  return launch_certify(h, B, *in, controls, act_tol, *out, pick_stream(h, stream));
+  if (act_tol != act_tol) return fail(BMPC_ERR_INVALID, "act_tol is NaN");
+  return eval_device(CERTIFY, h, B, in, controls, act_tol, out, slots_of(out), stream);
 }
 
 int bmpc_certify(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol, const bmpc_cert_out* out) {
-  if (int rc = check_certify(h, B, in, controls, act_tol, out); rc <= 0) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B, H = (size_t)h->dev.h;
-  // the two int32 outputs share one double each pair of instances at the end of the fp64 block
-  const size_t o_s = 0, o_r = o_s + (out->summary ? n * 4 : 0), o_l = o_r + (out->resid ? n * H * 12 : 0),
-               o_n = o_l + (out->lam ? n * H * 36 : 0), o_t = o_n + (out->n_active ? (n + 1) / 2 : 0),
-               tot = o_t + (out->status ? (n + 1) / 2 : 0);
-  HIP_TRY(h->eval_out.ensure(tot));
-  bmpc_inputs din;
-  if (int rc = stage_evaluate_inputs(h, B, in, controls, &din); rc != BMPC_OK) return rc;
-  hipStream_t st = h->stream;
-  double* d = h->eval_out.p;
-  const bmpc_cert_out dout = {out->lam ? d + o_l : nullptr, out->resid ? d + o_r : nullptr, out->summary ? d + o_s : nullptr,
-                              out->n_active ? (int32_t*)(d + o_n) : nullptr, out->status ? (int32_t*)(d + o_t) : nullptr};
-  if (int rc = launch_certify(h, B, din, h->controls.p, act_tol, dout, st); rc != BMPC_OK) return rc;
-  if (out->summary) HIP_TRY(hipMemcpyAsync(out->summary, dout.summary, n * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (out->resid) HIP_TRY(hipMemcpyAsync(out->resid, dout.resid, n * H * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (out->lam) HIP_TRY(hipMemcpyAsync(out->lam, dout.lam, n * H * 36 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (out->n_active) HIP_TRY(hipMemcpyAsync(out->n_active, dout.n_active, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (out->status) HIP_TRY(hipMemcpyAsync(out->status, dout.status, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return BMPC_OK;
+  if (act_tol != act_tol) return fail(BMPC_ERR_INVALID, "act_tol is NaN");
+  return eval_host(CERTIFY, h, B, in, controls, act_tol, out, slots_of(out));
 }
 
 static bmpc::LowLevelParams ll_params(const bmpc_params& p) {

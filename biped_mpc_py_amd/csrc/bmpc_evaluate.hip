@@ -38,6 +38,9 @@
 namespace bmpc {
 
 constexpr int EVAL_NT = 256;                   // lanes per workgroup (4 waves; no lane talks to another wave)
+// lanes per instance at horizon h (one lane per step, rounded up to a power of two that divides the wave): THE rule for the
+// kernels (eval_lane), the launch grid (bmpc_capi.hip) and the emulation's grid (tests/emu)
+constexpr int eval_lanes(const int h) { return h <= 16 ? 16 : (h <= 32 ? 32 : 64); }
 
 struct EvalParams {
   int h, half;
@@ -121,7 +124,7 @@ struct EvalLane {            // where a lane stands: its group of L lanes = its 
 
 __device__ __forceinline__ EvalLane eval_lane(const int h, const int B) {
   EvalLane t;
-  t.L = h <= 16 ? 16 : (h <= 32 ? 32 : 64);
+  t.L = eval_lanes(h);
   t.lane = threadIdx.x & 63;
   t.gl = t.lane & (t.L - 1);                   // place in the group = step
   const long long grp = ((long long)blockIdx.x * EVAL_NT + threadIdx.x) / t.L;

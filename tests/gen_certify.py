@@ -97,9 +97,9 @@ def main():
             if args.measure:
                 import __graft_entry__ as ge
                 ge.build()
-                from tests.emu import emu_certify
+                from tests.emu import emu_eval
                 gg = dict(g, controls=U)
-                got = emu_certify.certify(ec.cparams_of(gg), **ec.kernel_args(gg), act_tol=tol)
+                got = emu_eval.certify(ec.cparams_of(gg), **ec.kernel_args(gg), act_tol=tol)
                 dev = {k: float(v.max()) for k, v in cc.deviations(got, {k: v for k, v in ref.items() if k != "slack" or kind.startswith("solver_")}).items()}
                 if not kind.startswith("solver_"):   # MEASURED_REL is taken over the sets that exist without a GPU
                     worst = max(worst, max(dev.values()))

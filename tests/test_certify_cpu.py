@@ -1,5 +1,5 @@
 """KKT certificate of given controls (include/bmpc.h `bmpc_certify*`) without a GPU: the kernel's source run on the CPU
-(tests/emu/bmpc_emu_certify.cpp) against the yardstick of tests/certify_cases.py (the oracle's matrices and SciPy's NNLS, read from
+(tests/emu/bmpc_emu_eval.cpp) against the yardstick of tests/certify_cases.py (the oracle's matrices and SciPy's NNLS, read from
 tests/golden/certify.npz), against the merged evaluation and gradient, the C ABI's struct and argument checks, and the Python
 surface."""
 import ctypes as C
@@ -26,13 +26,13 @@ needs_emu = pytest.mark.skipif(not _emu_available(), reason="host clang (ROCm) n
 def _cert(g, idx=None, args=None, **kw):
     import __graft_entry__ as ge
     ge.build()
-    from tests.emu import emu_certify
-    return emu_certify.certify(ec.cparams_of(g), **(args if args is not None else ec.kernel_args(g, idx)), **kw)
+    from tests.emu import emu_eval
+    return emu_eval.certify(ec.cparams_of(g), **(args if args is not None else ec.kernel_args(g, idx)), **kw)
 
 
 def _grad(g):
-    from tests.emu import emu_eval_grad
-    return emu_eval_grad.evaluate_grad(ec.cparams_of(g), **ec.kernel_args(g))
+    from tests.emu import emu_eval
+    return emu_eval.evaluate_grad(ec.cparams_of(g), **ec.kernel_args(g))
 
 
 def _eval(g):

@@ -1,5 +1,5 @@
 """Gradient of the evaluated cost (include/bmpc.h `bmpc_evaluate_grad*`) without a GPU: the kernel's source run on the CPU
-(tests/emu/bmpc_emu_eval_grad.cpp) against the oracle's matrices (tests/eval_grad_cases.py `yardstick`) and against the merged
+(tests/emu/bmpc_emu_eval.cpp) against the oracle's matrices (tests/eval_grad_cases.py `yardstick`) and against the merged
 evaluation, the C ABI's struct and argument checks, and the Python surface."""
 import ctypes as C
 import os
@@ -25,8 +25,8 @@ needs_emu = pytest.mark.skipif(not _emu_available(), reason="host clang (ROCm) n
 def _grad(g, idx=None, args=None, **kw):
     import __graft_entry__ as ge
     ge.build()
-    from tests.emu import emu_eval_grad
-    return emu_eval_grad.evaluate_grad(ec.cparams_of(g), **(args if args is not None else ec.kernel_args(g, idx)), **kw)
+    from tests.emu import emu_eval
+    return emu_eval.evaluate_grad(ec.cparams_of(g), **(args if args is not None else ec.kernel_args(g, idx)), **kw)
 
 
 def _eval(g, idx=None, args=None):

@@ -4,42 +4,29 @@ the merged evaluation and gradient, on the solver's own answers, behind a solve 
 
 `python -m tests.test_gpu_certify --dump FILE` solves every instance of cfg2 / cfg4 with both kernel families and writes
 their controls to FILE, for `python -m tests.gen_certify --solver-controls FILE` to put their yardstick into the fixture."""
+import functools
+
 import numpy as np
 import pytest
 
 from tests import certify_cases as cc
 from tests import eval_cases as ec
 from tests import util
+from tests import gpu_common
+from tests.gpu_common import (  # noqa: F401 (_built: the autouse fixture)
+    built as _built, dev_args as _dev_args, solver as _solver, synth_group as _synth_group)
 
 pytestmark = pytest.mark.gpu
 
 KEYS = cc.KEYS
+_identical = functools.partial(gpu_common.identical, keys=KEYS)
 FAMILIES = {"solver_dense": 1, "solver_stage": 2}            # bmpc_params.path
 SOLVER_SETS = ("cfg2_standing_h10", "cfg4_walking_h10")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
 
 
 @pytest.fixture(scope="module")
 def fx():
     return cc.load_fixture()
-
-
-def _solver(g, path=0, max_batch=None):
-    import biped_mpc_py_amd as bm
-    return bm.BatchSolver(cparams=ec.cparams_of(g, path), max_batch=max_batch or max(16, g["x_fb"].shape[0]))
-
-
-def _dev_args(a):
-    """kernel_args as CUDA tensors of the dtypes the device entries take."""
-    import torch
-    dt = dict(x_fb=np.float32, foot=np.float32, contact=np.uint8, phase=np.int32, controls=np.float32, x_cmd=np.float32, mu=np.float32,
-              x_ref=np.float32, foot_ref=np.float32)
-    return {k: None if v is None else torch.from_numpy(np.ascontiguousarray(np.asarray(v).astype(dt[k]))).cuda() for k, v in a.items()}
 
 
 def _both(solver, a, act_tol):
@@ -49,16 +36,6 @@ def _both(solver, a, act_tol):
     dev = solver.certify_device(**_dev_args(a), act_tol=act_tol)
     torch.cuda.synchronize()
     return host, {k: dev[k].cpu().numpy() for k in KEYS}
-
-
-def _identical(x, y, where=""):
-    for k in KEYS:
-        assert np.array_equal(x[k], y[k], equal_nan=True), (where, k)
-
-
-def _synth_group(B, h, gait, seed):
-    s = util.synth_batch(B, h, seed, gait=gait)
-    return ec._group(h, s["half"], None, s["x_fb"], s["foot"], s["contact"], s["phase"], s["x_cmd"], np.zeros((B, h, 12)))
 
 
 def test_optima_and_worse_plans_match_the_yardstick_through_both_entries(fx):

@@ -1,34 +1,21 @@
 """Evaluation of given controls on the MI355X (`bmpc_evaluate`, `bmpc_evaluate_device`; include/bmpc.h ABI 13) against the oracle's
 matrices (tests/eval_cases.py `yardstick`), at scale, behind a solve, and timed against the solve."""
+import functools
+
 import numpy as np
 import pytest
 
 from tests import eval_cases as ec
 from tests import refs_cases as rc
 from tests import util
+from tests import gpu_common
+from tests.gpu_common import (  # noqa: F401 (_built: the autouse fixture)
+    built as _built, dev_args as _dev_args, solver as _solver)
 
 pytestmark = pytest.mark.gpu
 
 KEYS = ("cost", "objective", "violation", "states")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-
-
-def _solver(g, path=0, max_batch=None):
-    import biped_mpc_py_amd as bm
-    return bm.BatchSolver(cparams=ec.cparams_of(g, path), max_batch=max_batch or max(16, g["x_fb"].shape[0]))
-
-
-def _dev_args(a):
-    """kernel_args as CUDA tensors of the dtypes the device entries take."""
-    import torch
-    dt = dict(x_fb=np.float32, foot=np.float32, contact=np.uint8, phase=np.int32, controls=np.float32, x_cmd=np.float32, mu=np.float32,
-              x_ref=np.float32, foot_ref=np.float32)
-    return {k: None if v is None else torch.from_numpy(np.ascontiguousarray(np.asarray(v).astype(dt[k]))).cuda() for k, v in a.items()}
+_identical = functools.partial(gpu_common.identical, keys=KEYS)
 
 
 def _both(solver, a):
@@ -38,11 +25,6 @@ def _both(solver, a):
     dev = solver.evaluate_device(**_dev_args(a), want_states=True)
     torch.cuda.synchronize()
     return host, {k: dev[k].cpu().numpy() for k in KEYS}
-
-
-def _identical(x, y, where=""):
-    for k in KEYS:
-        assert np.array_equal(x[k], y[k], equal_nan=True), (where, k)
 
 
 def test_case_sets_against_the_yardstick_through_both_entries():

@@ -1,35 +1,22 @@
 """Gradient of the evaluated cost on the MI355X (`bmpc_evaluate_grad`, `bmpc_evaluate_grad_device`, `BatchSolver.cost_torch`) against the
 oracle's matrices (tests/eval_grad_cases.py `yardstick`), against the merged evaluation, behind a solve, through autograd, on the
 solver's own optima at scale, and timed next to the evaluation."""
+import functools
+
 import numpy as np
 import pytest
 
 from tests import eval_cases as ec
 from tests import eval_grad_cases as gc
 from tests import util
+from tests import gpu_common
+from tests.gpu_common import (  # noqa: F401 (_built: the autouse fixture)
+    built as _built, dev_args as _dev_args, solver as _solver, synth_group as _synth_group)
 
 pytestmark = pytest.mark.gpu
 
 KEYS = gc.KEYS
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-
-
-def _solver(g, path=0, max_batch=None):
-    import biped_mpc_py_amd as bm
-    return bm.BatchSolver(cparams=ec.cparams_of(g, path), max_batch=max_batch or max(16, g["x_fb"].shape[0]))
-
-
-def _dev_args(a):
-    """kernel_args as CUDA tensors of the dtypes the device entries take."""
-    import torch
-    dt = dict(x_fb=np.float32, foot=np.float32, contact=np.uint8, phase=np.int32, controls=np.float32, x_cmd=np.float32, mu=np.float32,
-              x_ref=np.float32, foot_ref=np.float32)
-    return {k: None if v is None else torch.from_numpy(np.ascontiguousarray(np.asarray(v).astype(dt[k]))).cuda() for k, v in a.items()}
+_identical = functools.partial(gpu_common.identical, keys=KEYS)
 
 
 def _both(solver, a):
@@ -41,11 +28,6 @@ def _both(solver, a):
     ev = solver.evaluate_device(**d)
     torch.cuda.synchronize()
     return host, {k: dev[k].cpu().numpy() for k in KEYS}, ev["cost"].cpu().numpy()
-
-
-def _identical(x, y, where=""):
-    for k in KEYS:
-        assert np.array_equal(x[k], y[k], equal_nan=True), (where, k)
 
 
 def test_case_sets_against_the_yardstick_through_both_entries():
@@ -100,11 +82,6 @@ def test_gradient_is_the_difference_of_the_merged_evaluation():
         cost_of = lambda c: solver.evaluate(**dict(a, controls=c))["cost"]
         gc.check_identity(cost_of, solver.evaluate_grad(**dict(a, controls=U))["grad_u"], g, U, D, g["name"])
         solver.close()
-
-
-def _synth_group(B, h, gait, seed):
-    s = util.synth_batch(B, h, seed, gait=gait)
-    return ec._group(h, s["half"], None, s["x_fb"], s["foot"], s["contact"], s["phase"], s["x_cmd"], np.zeros((B, h, 12)))
 
 
 def test_queued_behind_a_solve_on_the_same_stream():

@@ -5,34 +5,29 @@ spilling while the document said otherwise -- this test is what keeps the two in
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from tests import isa
+
+HIPCC = isa.HIPCC
 
 
 @pytest.fixture(scope="module")
-def isa_text(tmp_path_factory):
-    """The gfx950 ISA + code object metadata of every kernel, compiled once for the three tests below."""
-    import __graft_entry__ as ge
-    out = str(tmp_path_factory.mktemp("isa") / "bmpc.s")
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                           "--cuda-device-only", "-S", os.path.join(ge.CSRC, "bmpc_capi.hip"), "-o", out] + ge.KERNEL_FLAGS,
-                          cwd=ge.CSRC, stderr=subprocess.DEVNULL)
-    return open(out).read()
+def isa_text():
+    """The gfx950 ISA + code object metadata of every kernel, compiled once for the tests below (tests/isa.py)."""
+    return isa.compile_isa("bmpc_capi.hip")
 
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which(HIPCC)), reason="hipcc not available")
 def test_no_spills_and_two_waves_per_simd(isa_text):
     text = isa_text
     seen = {}
-    for entry in re.split(r"\n\s+- (?=\.agpr_count:)", text)[1:]:          # one metadata entry per kernel
-        m = re.search(r"\.name:\s+\S*solve_kernelILi(\d+)EE", entry)       # (not the diagnostics build solve_kernel_prof)
+    kernels = isa.metadata(text)                                           # one metadata entry per kernel
+    for name, meta in kernels.items():
+        m = re.match(r"\S*solve_kernelILi(\d+)EE", name)                   # (not the diagnostics build solve_kernel_prof)
         if m:
-            seen[int(m.group(1))] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\n", entry.split(".wavefront_size")[0])
-                                     if k != "offset" and k != "size"}
+            seen[int(m.group(1))] = meta
     assert sorted(seen) == [8, 10, 12, 14, 16, 18, 20], seen
     for h, meta in seen.items():
         # Round 6: NOTHING spills up to h = 18, and h = 20 keeps 4 dwords (a set-up index, an LDS address, one f64 -- reloaded at
@@ -54,11 +49,10 @@ def test_no_spills_and_two_waves_per_simd(isa_text):
     # the stage-structured family: one wave per instance up to h = 24, two from h = 26; what an instance holds in LDS
     # decides how many share a CU, and no variant spills (two waves halve the steps a lane owns)
     stage = {}
-    for entry in re.split(r"\n\s+- (?=\.agpr_count:)", text)[1:]:
-        m = re.search(r"\.name:\s+\S*stage_kernelILi(\d+)ELi(\d+)EE", entry)
+    for name, meta in kernels.items():
+        m = re.match(r"\S*stage_kernelILi(\d+)ELi(\d+)EE", name)
         if m:
-            stage[(int(m.group(1)), int(m.group(2)))] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\n", entry.split(".wavefront_size")[0])
-                                                         if k != "offset" and k != "size"}
+            stage[(int(m.group(1)), int(m.group(2)))] = meta
     assert sorted(stage) == [(2, 1), (3, 1), (3, 2), (4, 1), (4, 2), (5, 1)], stage
     for (n_p, n_w), meta in stage.items():
         lds = int(meta["group_segment_fixed_size"])

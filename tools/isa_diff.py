@@ -12,8 +12,9 @@ META = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spil
         "group_segment_fixed_size")
 
 
-def functions(text):
-    """{symbol: [instruction lines]} of every `.type sym,@function` of the listing."""
+def functions(text, normalise=True):
+    """{symbol: [instruction lines]} of every `.type sym,@function` of the listing.  `normalise`: local labels numbered by order of
+    appearance and runs of blanks collapsed (what a comparison wants); without it the lines keep the listing's own labels."""
     out, cur, labels = {}, None, {}
     names = set(re.findall(r"^\s*\.type\s+(\S+),@function", text, flags=re.M))
     for ln in text.split("\n"):
@@ -29,9 +30,11 @@ def functions(text):
         ln = ln.split(";")[0].strip()
         if not ln or (ln.startswith(".") and not re.match(r"^\.L\w+:", ln)):
             continue                                    # comments, directives, .loc / .file markers
-        # local labels (.LBB3_7, .LJTI3_0 ...): numbered in order of first appearance within the function
-        ln = re.sub(r"\.L[A-Za-z]\w*", lambda k: labels.setdefault(k.group(0), ".L%d" % len(labels)), ln)
-        cur.append(re.sub(r"\s+", " ", ln))
+        if normalise:
+            # local labels (.LBB3_7, .LJTI3_0 ...): numbered in order of first appearance within the function
+            ln = re.sub(r"\.L[A-Za-z]\w*", lambda k: labels.setdefault(k.group(0), ".L%d" % len(labels)), ln)
+            ln = re.sub(r"\s+", " ", ln)
+        cur.append(ln)
     return out
 
 
