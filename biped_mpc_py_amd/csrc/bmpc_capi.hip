@@ -200,9 +200,17 @@ int make_dev_params(const bmpc_params& p, bmpc::DevParams* d) {
 
 // page-locked host memory (the staging of the host-pointer entry points: copies to and from it run at the full PCIe rate
 // and asynchronously, which pageable memory does not allow)
-struct PinnedBuf {
+// (the three buffer types below free what they hold when they go -- with the handle, in bmpc_destroy -- and are not copied)
+struct NoCopy {
+  NoCopy() = default;
+  NoCopy(const NoCopy&) = delete;
+  NoCopy& operator=(const NoCopy&) = delete;
+};
+
+struct PinnedBuf : NoCopy {
   char* p = nullptr;
   size_t n = 0;
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= n) return hipSuccess;
     if (p) (void)hipHostFree(p);
@@ -213,18 +221,21 @@ struct PinnedBuf {
     if (e == hipSuccess) n = bytes;
     return e;
   }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
 };
 
 // The same for memory the CALLER holds pointers into (the I/O block of bmpc_host_io): a block that has to grow is not freed but
 // retired until the handle goes -- a view of the old layout that a caller still holds must not dangle --, and it grows by half at
 // least, so that what is retired stays below twice what is in use.
-struct RetiringPinnedBuf {
+struct RetiringPinnedBuf : NoCopy {
   char* p = nullptr;
   size_t n = 0;
   static constexpr int MAX_RETIRED = 64;
   char* retired[MAX_RETIRED] = {};
   int n_retired = 0;
+  ~RetiringPinnedBuf() {
+    if (p) (void)hipHostFree(p);
+    for (int i = 0; i < n_retired; ++i) (void)hipHostFree(retired[i]);
+  }
   hipError_t ensure(size_t bytes) {
     if (bytes <= n) return hipSuccess;
     size_t cap = n + n / 2;
@@ -239,17 +250,13 @@ struct RetiringPinnedBuf {
     p = q; n = cap;
     return hipSuccess;
   }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    for (int i = 0; i < n_retired; ++i) (void)hipHostFree(retired[i]);
-    p = nullptr; n = 0; n_retired = 0;
-  }
 };
 
 template <typename T>
-struct DevBuf {
+struct DevBuf : NoCopy {
   T* p = nullptr;
   size_t n = 0;
+  ~DevBuf() { if (p) (void)hipFree(p); }
   hipError_t ensure(size_t count) {
     if (count <= n) return hipSuccess;
     if (p) (void)hipFree(p);
@@ -258,36 +265,85 @@ struct DevBuf {
     if (e == hipSuccess) n = count;
     return e;
   }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
 
-// Offsets of the packed arrays of n instances, every array `align`-byte aligned (a power of two).  Inputs: x_fb, foot, phase
-// [, x_cmd] [, mu], contact [, x_ref] [, foot_ref] (the last two after everything else: without them the layout is the one the
-// handle's I/O block has always had); outputs: controls [, states] in elements of out_elem bytes (f32 or f64), iters, status, nfactor,
-// residuals.
-struct PackedLayout {
-  size_t i_xfb = 0, i_foot = 0, i_phase = 0, i_xcmd = 0, i_mu = 0, i_con = 0, i_xref = 0, i_fref = 0, in_bytes = 0;
-  size_t o_u = 0, o_s = 0, o_it = 0, o_st = 0, o_nf = 0, o_rs = 0, out_bytes = 0;
+// ---- The per-instance arrays of a solve, stated once: everything that packs, stages, lays out or views them walks these tables.
+
+// elements per instance (fixed + per_step * h) and bytes per element of one array
+struct Width {
+  size_t fixed, per_step, elem;
+  constexpr size_t count(size_t H) const { return fixed + per_step * H; }
+  constexpr size_t bytes(size_t H) const { return count(H) * elem; }        // per instance
 };
-PackedLayout packed_layout(size_t n, size_t H, bool x_cmd, bool mu, bool states, size_t align, size_t out_elem,
-                           bool x_ref = false, bool foot_ref = false) {
-  auto up = [align](size_t v) { return (v + align - 1) & ~(align - 1); };
+
+// The buffers of one solve launch: device-addressable pointers (on the I/O path some point into mapped page-locked host
+// memory), null where bmpc_solve_inputs_device allows it.  controls64 / states64: fp64 outputs that take the place of controls /
+// states (bmpc::WarmArgs).
+struct SolveIO {
+  bmpc_inputs in = {};               // (x_ref, foot_ref: supplied references or null)
+  float *controls = nullptr, *states = nullptr, *resid = nullptr;
+  int32_t *iters = nullptr, *status = nullptr, *nfactor = nullptr;
+  double *controls64 = nullptr, *states64 = nullptr;
+};
+
+// A row: where the array's pointer sits in its descriptor (inputs: bmpc_inputs; outputs: SolveIO) and in bmpc_host_views (NO_VIEW:
+// the I/O block never holds it), its width (elem 0: f32 or f64, as the caller of the layout chooses, and widened from the
+// kernels' f32 by the host-pointer entries), and whether a packed block always has room for it.  The rows are in the order
+// of the packed blocks, which the enums name.  A further input is a row here, a bmpc_inputs member and its kernel parameter.
+struct Field { size_t member, view; Width w; bool always; };
+constexpr size_t NO_VIEW = ~(size_t)0;
+enum { I_XFB, I_FOOT, I_PHASE, I_XCMD, I_MU, I_CON, I_XREF, I_FREF, N_IN };
+enum { O_U, O_S, O_IT, O_ST, O_NF, O_RS, N_OUT };
+#define BMPC_IN(m) offsetof(bmpc_inputs, m), offsetof(bmpc_host_views, m)
+constexpr Field IN[N_IN] = {
+    {BMPC_IN(x_fb), {12, 0, 4}, true},   {BMPC_IN(foot), {6, 0, 4}, true}, {BMPC_IN(phase), {1, 0, 4}, true},
+    {BMPC_IN(x_cmd), {12, 0, 4}, false}, {BMPC_IN(mu), {0, 2, 4}, false},  {BMPC_IN(contact), {0, 2, 1}, true},
+    {offsetof(bmpc_inputs, x_ref), NO_VIEW, {0, 12, 4}, false}, {offsetof(bmpc_inputs, foot_ref), NO_VIEW, {0, 6, 4}, false}};
+#undef BMPC_IN
+#define BMPC_OUT(m, v) offsetof(SolveIO, m), offsetof(bmpc_host_views, v)
+constexpr Field OUT[N_OUT] = {{BMPC_OUT(controls, controls), {0, 12, 0}, true}, {BMPC_OUT(states, states), {0, 13, 0}, false},
+                              {BMPC_OUT(iters, iters), {1, 0, 4}, true},        {BMPC_OUT(status, status), {1, 0, 4}, true},
+                              {BMPC_OUT(nfactor, nfactor), {1, 0, 4}, true},    {BMPC_OUT(resid, residuals), {2, 0, 4}, true}};
+#undef BMPC_OUT
+
+// the pointer members of the descriptors, by offset
+const void* get_ptr(const void* desc, size_t member) { const void* p; std::memcpy(&p, (const char*)desc + member, sizeof(p)); return p; }
+void set_ptr(void* desc, size_t member, const void* p) { std::memcpy((char*)desc + member, &p, sizeof(p)); }
+
+// Offsets of the packed arrays of n instances, every array `align`-byte aligned (a power of two): inputs and outputs in the
+// order of the tables; has_in / has_out: bit i set where row i is there (the `always` rows are), controls and states in elements
+// of out_elem bytes.  (x_ref and foot_ref come after everything else: without them the layout is the one the handle's I/O block
+// has always had.)
+struct PackedLayout {
+  size_t H = 0, out_elem = 0;
+  unsigned has_in = 0, has_out = 0;
+  size_t in[N_IN] = {}, in_bytes = 0, out[N_OUT] = {}, out_bytes = 0;
+  size_t stride(const Field& f) const { return f.w.count(H) * (f.w.elem ? f.w.elem : out_elem); }   // bytes per instance
+  // byte offset of input / output array i, from instance lo on
+  size_t in_at(int i, size_t lo) const { return in[i] + lo * stride(IN[i]); }
+  size_t out_at(int i, size_t lo) const { return out[i] + lo * stride(OUT[i]); }
+};
+PackedLayout packed_layout(size_t n, size_t H, unsigned has_in, unsigned has_out, size_t align, size_t out_elem) {
   PackedLayout L;
-  L.i_foot = up(L.i_xfb + n * 12 * 4);
-  L.i_phase = up(L.i_foot + n * 6 * 4);
-  L.i_xcmd = up(L.i_phase + n * 4);
-  L.i_mu = up(L.i_xcmd + (x_cmd ? n * 12 * 4 : 0));
-  L.i_con = up(L.i_mu + (mu ? n * H * 2 * 4 : 0));
-  L.i_xref = up(L.i_con + n * H * 2);
-  L.i_fref = up(L.i_xref + (x_ref ? n * H * 12 * 4 : 0));
-  L.in_bytes = up(L.i_fref + (foot_ref ? n * H * 6 * 4 : 0));
-  L.o_s = up(L.o_u + n * H * 12 * out_elem);
-  L.o_it = up(L.o_s + (states ? n * H * 13 * out_elem : 0));
-  L.o_st = up(L.o_it + n * 4);
-  L.o_nf = up(L.o_st + n * 4);
-  L.o_rs = up(L.o_nf + n * 4);
-  L.out_bytes = up(L.o_rs + n * 2 * 4);
+  L.H = H; L.out_elem = out_elem; L.has_in = has_in; L.has_out = has_out;
+  auto lay = [&](const Field* f, int rows, unsigned& has, size_t* off) {
+    size_t at = 0;
+    for (int i = 0; i < rows; ++i) {
+      if (f[i].always) has |= 1u << i;
+      off[i] = at;
+      at = (at + (has >> i & 1 ? n * L.stride(f[i]) : 0) + align - 1) & ~(align - 1);
+    }
+    return at;
+  };
+  L.in_bytes = lay(IN, N_IN, L.has_in, L.in);
+  L.out_bytes = lay(OUT, N_OUT, L.has_out, L.out);
   return L;
+}
+// the rows of IN a descriptor holds an array for
+unsigned present(const bmpc_inputs& in) {
+  unsigned has = 0;
+  for (int i = 0; i < N_IN; ++i) has |= get_ptr(&in, IN[i].member) ? 1u << i : 0;
+  return has;
 }
 
 }  // namespace
@@ -323,15 +379,11 @@ struct bmpc_handle_s {
   DevBuf<double> io_states;         // fp64 states of a batch in HBM, on their way to the I/O block by copy engine
   hipEvent_t cev_in = nullptr;      // the I/O block's inputs have arrived
   int io_gen = 0;                   // moves with every bmpc_host_io call (bmpc_host_io_generation)
-  struct IoLayout : PackedLayout {
-    int B = 0;
-    bool x_cmd = false, mu = false, states = false;
-  } io;
-  DevBuf<float> x_fb, foot, x_cmd, mu, controls, states, resid;
-  DevBuf<float> x_ref, foot_ref;    // supplied references of bmpc_debug_assemble_inputs / bmpc_evaluate
+  struct IoLayout : PackedLayout { int B = 0; } io;
+  DevBuf<char> stage[N_IN];         // host inputs on the device, one buffer per row of IN (stage_inputs, the low-level host entries)
+  DevBuf<float> controls;           // host controls of the evaluation family; what an assembly launch stores
   DevBuf<double> eval_out;          // results of bmpc_evaluate (host pointers) on their way back
-  DevBuf<uint8_t> contact;
-  DevBuf<int32_t> phase, iters, status, nfactor;
+  DevBuf<int32_t> status;           // the rescue pass's, where the caller asks for none
   DevBuf<double> dbg;
   DevBuf<float> ll_q, ll_qd, ll_pf, ll_u0, ll_tau;
   DevBuf<double> ll_t;
@@ -358,28 +410,6 @@ namespace {
 // stage-structured kernels (bmpc_stage.hip).
 #define BMPC_DENSE_HORIZONS(X) X(8) X(10) X(12) X(14) X(16) X(18) X(20)
 
-// The buffers of one solve launch, as bmpc_solve_batch_device takes them: device-addressable pointers (on the I/O path some
-// point into mapped page-locked host memory), null where that entry point allows it.  controls64 / states64: fp64 outputs
-// that take the place of controls / states (bmpc::WarmArgs).
-struct SolveIO {
-  const float* x_fb = nullptr;
-  const float* foot = nullptr;
-  const uint8_t* contact = nullptr;
-  const int32_t* phase = nullptr;
-  const float* x_cmd = nullptr;
-  const float* mu = nullptr;
-  const float* x_ref = nullptr;      // supplied references or null (bmpc_inputs; bmpc::WarmArgs)
-  const float* foot_ref = nullptr;
-  float* controls = nullptr;
-  float* states = nullptr;
-  int32_t* iters = nullptr;
-  float* resid = nullptr;
-  int32_t* status = nullptr;
-  int32_t* nfactor = nullptr;
-  double* controls64 = nullptr;
-  double* states64 = nullptr;
-};
-
 // One launch of either kernel family: the warm-start set-up (warm_per_inst doubles of solver state per instance), then
 // `kernel(args...)`, which launches the family's kernel with the parameter list both families share.
 template <typename Kernel>
@@ -387,7 +417,7 @@ int launch_family(bmpc_handle hd, int B, size_t warm_per_inst, const SolveIO& io
                   const int32_t* order, const int32_t* rescue_status, Kernel kernel) {
   // (the references go to every launch of the solve, the rescue pass included: it solves the same problem again)
   bmpc::WarmArgs warm = {nullptr, 0, 0, 0, 1.f, 0, dbg.assemble_only ? nullptr : order, rescue_status, io.controls64, io.states64,
-                         io.x_ref, io.foot_ref};
+                         io.in.x_ref, io.in.foot_ref};
   if (hd->warm_on && !dbg.assemble_only && !rescue_status) {   // (a rescue pass starts cold: the stored state is the dense family's)
     const size_t need = (size_t)B * warm_per_inst;
     if (need > hd->warm.n) hd->warm_valid = false;          // growing the buffer loses the stored state
@@ -399,7 +429,7 @@ int launch_family(bmpc_handle hd, int B, size_t warm_per_inst, const SolveIO& io
     warm.theta = hd->warm_theta;
     warm.adapt_start = hd->params.warm_adapt_start;
   }
-  kernel(hd->dev, B, io.x_fb, io.foot, io.contact, io.phase, io.x_cmd, io.mu, io.controls, io.states, io.iters, io.resid,
+  kernel(hd->dev, B, io.in.x_fb, io.in.foot, io.in.contact, io.in.phase, io.in.x_cmd, io.in.mu, io.controls, io.states, io.iters, io.resid,
          io.status, io.nfactor, dbg, warm);
   HIP_TRY(hipGetLastError());
   if (warm.buf) { hd->warm_valid = true; hd->warm_batch = B; }
@@ -479,10 +509,9 @@ int check_batch(bmpc_handle h, int B) {
 }
 
 // check_batch and the arrays a solve cannot do without (foot: unless foot_ref takes its place)
-int check_common(bmpc_handle h, int B, const void* x_fb, const void* foot, const void* contact, const void* phase,
-                 const void* controls, const void* foot_ref = nullptr) {
+int check_common(bmpc_handle h, int B, const bmpc_inputs& in, const void* controls) {
   const int rc = check_batch(h, B);
-  if (rc > 0 && (!x_fb || !(foot || foot_ref) || !contact || !phase || !controls))
+  if (rc > 0 && (!in.x_fb || !(in.foot || in.foot_ref) || !in.contact || !in.phase || !controls))
     return fail(BMPC_ERR_INVALID, "x_fb, foot (or foot_ref), contact, phase and controls must be non-null");
   return rc;
 }
@@ -492,7 +521,7 @@ int check_common(bmpc_handle h, int B, const void* x_fb, const void* foot, const
 //  out in chunks records ev0 before its first kernel and ev1 after its last, so bmpc_last_kernel_ms spans them all)
 int solve_device_ordered(bmpc_handle h, int B, const SolveIO& io, void* stream, const int32_t* order, int ev = 3) {
   const void* controls = io.controls64 ? static_cast<const void*>(io.controls64) : static_cast<const void*>(io.controls);
-  if (int rc = check_common(h, B, io.x_fb, io.foot, io.contact, io.phase, controls, io.foot_ref); rc <= 0) return rc;
+  if (int rc = check_common(h, B, io.in, controls); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = pick_stream(h, stream);
   bmpc::DebugOut dbg = {nullptr, nullptr, nullptr, nullptr, h->prof_dev, 0};
@@ -547,22 +576,13 @@ int bail(bmpc_handle h, int issued, int code) {
     if (e_ != hipSuccess) return bail(h, issued, fail(BMPC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_))); \
   } while (0)
 
-// The arrays of instances lo.. in packed blocks `in` / `out` laid out by L, but for controls and states (f32 or f64)
-SolveIO packed_io(const PackedLayout& L, const char* in, char* out, size_t lo, size_t H, bool x_cmd, bool mu, bool x_ref = false,
-                  bool foot_ref = false) {
+// The arrays of instances lo.. in packed blocks `in` / `out` laid out by L, but for controls and states (f32 or f64: the caller's)
+SolveIO packed_io(const PackedLayout& L, const char* in, char* out, size_t lo) {
   SolveIO io;
-  io.x_fb = reinterpret_cast<const float*>(in + L.i_xfb) + lo * 12;
-  io.foot = reinterpret_cast<const float*>(in + L.i_foot) + lo * 6;
-  io.contact = reinterpret_cast<const uint8_t*>(in + L.i_con) + lo * H * 2;
-  io.phase = reinterpret_cast<const int32_t*>(in + L.i_phase) + lo;
-  if (x_cmd) io.x_cmd = reinterpret_cast<const float*>(in + L.i_xcmd) + lo * 12;
-  if (mu) io.mu = reinterpret_cast<const float*>(in + L.i_mu) + lo * H * 2;
-  if (x_ref) io.x_ref = reinterpret_cast<const float*>(in + L.i_xref) + lo * H * 12;
-  if (foot_ref) io.foot_ref = reinterpret_cast<const float*>(in + L.i_fref) + lo * H * 6;
-  io.iters = reinterpret_cast<int32_t*>(out + L.o_it) + lo;
-  io.resid = reinterpret_cast<float*>(out + L.o_rs) + lo * 2;
-  io.status = reinterpret_cast<int32_t*>(out + L.o_st) + lo;
-  io.nfactor = reinterpret_cast<int32_t*>(out + L.o_nf) + lo;
+  for (int i = 0; i < N_IN; ++i)
+    if (L.has_in >> i & 1) set_ptr(&io.in, IN[i].member, in + L.in_at(i, lo));
+  for (int i = 0; i < N_OUT; ++i)
+    if (OUT[i].w.elem) set_ptr(&io, OUT[i].member, out + L.out_at(i, lo));
   return io;
 }
 
@@ -578,10 +598,10 @@ SolveIO packed_io(const PackedLayout& L, const char* in, char* out, size_t lo, s
 // Ordering: the chunk streams wait for what was queued on the handle's own stream before the call, and the call returns with
 // every chunk complete.
 template <typename T>
-int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact, const int32_t* phase,
-               const float* x_cmd, const float* mu, T* controls, T* states, int32_t* iters, float* residuals, int32_t* status,
-               int32_t* nfactor, const float* x_ref = nullptr, const float* foot_ref = nullptr) {
-  if (int rc = check_common(h, B, x_fb, foot, contact, phase, controls, foot_ref); rc <= 0) return rc;
+int solve_host(bmpc_handle h, int B, const bmpc_inputs& in, T* controls, T* states, int32_t* iters, float* residuals,
+               int32_t* status, int32_t* nfactor) {
+  if (int rc = check_common(h, B, in, controls); rc <= 0) return rc;
+  void* const dst[N_OUT] = {controls, states, iters, status, nfactor, residuals};      // (the order of OUT)
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B, H = (size_t)h->dev.h;
   const bool timing = h->host_timing;                                 // (diagnostics: where a host-pointer call spends its time)
@@ -593,7 +613,7 @@ int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const
   struct Chunk { PackedLayout L; size_t in, out; } ck[bmpc_handle_s::HOST_CHUNKS];
   size_t in_bytes = 0, out_bytes = 0;
   for (int c = 0; c < plan.n; ++c) {
-    ck[c] = {packed_layout(plan.nb[c], H, x_cmd, mu, states, 16, 4, x_ref, foot_ref), in_bytes, out_bytes};
+    ck[c] = {packed_layout(plan.nb[c], H, present(in), states ? 1u << O_S : 0, 16, 4), in_bytes, out_bytes};
     in_bytes += ck[c].L.in_bytes;
     out_bytes += ck[c].L.out_bytes;
   }
@@ -610,22 +630,17 @@ int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const
     // chunks are still being packed)
     char* pin = h->pin_in.p + ck[c].in;
     char* din = h->dev_in.p + ck[c].in;
-    std::memcpy(pin + L.i_xfb, x_fb + lo * 12, nb * 12 * 4);
-    if (foot) std::memcpy(pin + L.i_foot, foot + lo * 6, nb * 6 * 4);
-    std::memcpy(pin + L.i_phase, phase + lo, nb * 4);
-    if (x_cmd) std::memcpy(pin + L.i_xcmd, x_cmd + lo * 12, nb * 12 * 4);
-    if (mu) std::memcpy(pin + L.i_mu, mu + lo * H * 2, nb * H * 2 * 4);
-    std::memcpy(pin + L.i_con, contact + lo * H * 2, nb * H * 2);
-    if (x_ref) std::memcpy(pin + L.i_xref, x_ref + lo * H * 12, nb * H * 12 * 4);
-    if (foot_ref) std::memcpy(pin + L.i_fref, foot_ref + lo * H * 6, nb * H * 6 * 4);
+    for (int i = 0; i < N_IN; ++i)
+      if (const void* src = get_ptr(&in, IN[i].member))
+        std::memcpy(pin + L.in[i], static_cast<const char*>(src) + lo * IN[i].w.bytes(H), nb * IN[i].w.bytes(H));
     hipStream_t st = h->cstream[c];
     issued = c + 1;
     CHUNK_TRY(hipMemcpyAsync(din, pin, L.in_bytes, hipMemcpyHostToDevice, st));
     char* dout = h->dev_out.p + ck[c].out;
-    SolveIO io = packed_io(L, din, dout, 0, H, x_cmd, mu, x_ref, foot_ref);
-    if (!foot) io.foot = nullptr;               // (foot_ref given: the kernels never read foot)
-    io.controls = reinterpret_cast<float*>(dout + L.o_u);
-    if (states) io.states = reinterpret_cast<float*>(dout + L.o_s);
+    SolveIO io = packed_io(L, din, dout, 0);
+    if (!in.foot) io.in.foot = nullptr;         // (foot_ref given: the kernels never read foot)
+    io.controls = reinterpret_cast<float*>(dout + L.out[O_U]);
+    if (states) io.states = reinterpret_cast<float*>(dout + L.out[O_S]);
     if (int rc = solve_device_ordered(h, (int)nb, io, st, h->order, plan.events(c)); rc != BMPC_OK) return bail(h, issued, rc);
     // (the copy engine moves a chunk at ~50 GB/s while the later chunks solve; stores of the kernels themselves into mapped host
     //  memory sustain ~8.6 GB/s on MI355X -- measured, round 5 -- which a 4096-instance batch's 4 MB would just fit under, with
@@ -644,16 +659,15 @@ int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const
     t_wait += tw1 - tw0; t_last_wait = tw1 - tw0;
     if (timing) std::fprintf(stderr, "[bmpc host path]   chunk %d ready %.0f us after the call began (waited %.0f)\n", c, tw1 - t_begin, tw1 - tw0);
     const char* src = h->pin_out.p + ck[c].out;
-    auto put = [&](T* dst, const float* from, size_t cnt) {
-      if constexpr (sizeof(T) == sizeof(float)) std::memcpy(dst, from, cnt * sizeof(float));
-      else for (size_t q = 0; q < cnt; ++q) dst[q] = (T)from[q];
-    };
-    put(controls + lo * H * 12, reinterpret_cast<const float*>(src + L.o_u), nb * H * 12);
-    if (states) put(states + lo * H * 13, reinterpret_cast<const float*>(src + L.o_s), nb * H * 13);
-    if (iters) std::memcpy(iters + lo, src + L.o_it, nb * 4);
-    if (status) std::memcpy(status + lo, src + L.o_st, nb * 4);
-    if (nfactor) std::memcpy(nfactor + lo, src + L.o_nf, nb * 4);
-    if (residuals) std::memcpy(residuals + lo * 2, src + L.o_rs, nb * 2 * 4);
+    for (int i = 0; i < N_OUT; ++i) {
+      if (!dst[i]) continue;
+      const size_t cnt = OUT[i].w.count(H);
+      const char* from = src + L.out[i];
+      if (sizeof(T) != sizeof(float) && !OUT[i].w.elem) {     // controls, states: widened
+        T* to = static_cast<T*>(dst[i]) + lo * cnt;
+        for (size_t q = 0; q < nb * cnt; ++q) to[q] = (T)reinterpret_cast<const float*>(from)[q];
+      } else std::memcpy(static_cast<char*>(dst[i]) + lo * cnt * sizeof(float), from, nb * cnt * sizeof(float));
+    }
     if (timing) { const double tu = now() - tw1; t_unpack += tu; t_last_unpack = tu; }
   }
   if (timing)
@@ -662,30 +676,30 @@ int solve_host(bmpc_handle h, int B, const float* x_fb, const float* foot, const
   return BMPC_OK;
 }
 
-// Host inputs onto the device, queued on the handle's own stream: staged through the handle's scratch arrays (the synchronous
-// host entries of the evaluation family and bmpc_debug_assemble_inputs).  `controls`: host controls to stage with them, or null
-// (the scratch array is sized either way: the assembly launch stores there).  `din`: the descriptor of the copies.
+// Host array `src` of `count` elements onto the device: the handle's buffer made large enough, the copy queued on the handle's
+// own stream; *dev: the copy, or null where src is.
+template <typename T, typename U>
+int upload(bmpc_handle h, DevBuf<T>& buf, const U* src, size_t count, const U** dev) {
+  *dev = nullptr;
+  if (!src) return BMPC_OK;
+  HIP_TRY(buf.ensure(count * sizeof(U) / sizeof(T)));
+  HIP_TRY(hipMemcpyAsync(buf.p, src, count * sizeof(U), hipMemcpyHostToDevice, h->stream));
+  *dev = reinterpret_cast<const U*>(buf.p);
+  return BMPC_OK;
+}
+
+// The inputs of a solve, host arrays, onto the device through the handle's staging buffers (the synchronous host entries of the
+// evaluation family and bmpc_debug_assemble_inputs).  `controls`: host controls to stage with them, or null (the scratch array is
+// sized either way: the assembly launch stores there).  `din`: the descriptor of the copies.
 int stage_inputs(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, bmpc_inputs* din) {
-  const size_t n = (size_t)B, H = (size_t)h->dev.h;
-  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->contact.ensure(n * H * 2));
-  HIP_TRY(h->phase.ensure(n)); HIP_TRY(h->controls.ensure(n * H * 12));
-  if (in.foot) HIP_TRY(h->foot.ensure(n * 6));
-  if (in.x_cmd) HIP_TRY(h->x_cmd.ensure(n * 12));
-  if (in.mu) HIP_TRY(h->mu.ensure(n * H * 2));
-  if (in.x_ref) HIP_TRY(h->x_ref.ensure(n * H * 12));
-  if (in.foot_ref) HIP_TRY(h->foot_ref.ensure(n * H * 6));
-  hipStream_t st = h->stream;
-  HIP_TRY(hipMemcpyAsync(h->x_fb.p, in.x_fb, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in.foot) HIP_TRY(hipMemcpyAsync(h->foot.p, in.foot, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->contact.p, in.contact, n * H * 2, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->phase.p, in.phase, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  if (controls) HIP_TRY(hipMemcpyAsync(h->controls.p, controls, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in.x_cmd) HIP_TRY(hipMemcpyAsync(h->x_cmd.p, in.x_cmd, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in.mu) HIP_TRY(hipMemcpyAsync(h->mu.p, in.mu, n * H * 2 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in.x_ref) HIP_TRY(hipMemcpyAsync(h->x_ref.p, in.x_ref, n * H * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  if (in.foot_ref) HIP_TRY(hipMemcpyAsync(h->foot_ref.p, in.foot_ref, n * H * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-  *din = {h->x_fb.p, in.foot ? h->foot.p : nullptr, h->contact.p, h->phase.p, in.x_cmd ? h->x_cmd.p : nullptr,
-          in.mu ? h->mu.p : nullptr, in.x_ref ? h->x_ref.p : nullptr, in.foot_ref ? h->foot_ref.p : nullptr};
+  const size_t n = (size_t)B, H = (size_t)h->dev.h, nu = n * OUT[O_U].w.count(H);
+  HIP_TRY(h->controls.ensure(nu));
+  for (int i = 0; i < N_IN; ++i) {
+    const char* d;
+    if (int rc = upload(h, h->stage[i], static_cast<const char*>(get_ptr(&in, IN[i].member)), n * IN[i].w.bytes(H), &d); rc != BMPC_OK) return rc;
+    set_ptr(din, IN[i].member, d);
+  }
+  if (controls) HIP_TRY(hipMemcpyAsync(h->controls.p, controls, nu * sizeof(float), hipMemcpyHostToDevice, h->stream));
   return BMPC_OK;
 }
 
@@ -693,9 +707,8 @@ int stage_inputs(bmpc_handle h, int B, const bmpc_inputs& in, const float* contr
 // of the handle's per-solve state involved.  The kernels differ (bmpc_evaluate.hip, bmpc_evaluate_grad.hip, bmpc_certify.hip);
 // the path around them is stated once here.  A further operation is a kernel, an EvalOp row, a slot table and two entries.
 
-// one member of an operation's output descriptor: the caller's pointer (null: not wanted), elements per instance
-// (fixed + per_step * h) and bytes per element
-struct OutSlot { void* p; size_t fixed, per_step, elem; };
+// one member of an operation's output descriptor: the caller's pointer (null: not wanted) and the array's width
+struct OutSlot { void* p; Width w; };
 template <size_t N> struct OutSlots { OutSlot s[N]; };
 
 // `launch`: the operation's kernel on device-addressable inputs; `out`: one pointer per slot, in the table's order
@@ -734,15 +747,15 @@ const EvalOp CERTIFY = {"null bmpc_cert_out", "bmpc_cert_out: at least one of la
 // the slot tables, in the member order of the descriptors (include/bmpc.h); a null descriptor gives all-null slots
 OutSlots<4> slots_of(const bmpc_eval_out* out) {
   const bmpc_eval_out o = out ? *out : bmpc_eval_out{};
-  return {{{o.cost, 1, 0, 8}, {o.objective, 1, 0, 8}, {o.states, 0, 13, 8}, {o.violation, 4, 0, 8}}};
+  return {{{o.cost, {1, 0, 8}}, {o.objective, {1, 0, 8}}, {o.states, {0, 13, 8}}, {o.violation, {4, 0, 8}}}};
 }
 OutSlots<3> slots_of(const bmpc_grad_out* out) {
   const bmpc_grad_out o = out ? *out : bmpc_grad_out{};
-  return {{{o.cost, 1, 0, 8}, {o.grad_u, 0, 12, 8}, {o.grad_x0, 12, 0, 8}}};
+  return {{{o.cost, {1, 0, 8}}, {o.grad_u, {0, 12, 8}}, {o.grad_x0, {12, 0, 8}}}};
 }
 OutSlots<5> slots_of(const bmpc_cert_out* out) {
   const bmpc_cert_out o = out ? *out : bmpc_cert_out{};
-  return {{{o.lam, 0, 36, 8}, {o.resid, 0, 12, 8}, {o.summary, 4, 0, 8}, {o.n_active, 1, 0, 4}, {o.status, 1, 0, 4}}};
+  return {{{o.lam, {0, 36, 8}}, {o.resid, {0, 12, 8}}, {o.summary, {4, 0, 8}}, {o.n_active, {1, 0, 4}}, {o.status, {1, 0, 4}}}};
 }
 
 // what every entry checks before a device is touched (and before the handle is read): an error code (< 0), BMPC_OK when there is
@@ -757,7 +770,7 @@ int check_eval(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, co
   bool any_out = false;
   for (const OutSlot& s : slots.s) any_out = any_out || s.p;
   if (!any_out) return fail(BMPC_ERR_INVALID, op.none_out);
-  return check_common(h, B, in->x_fb, in->foot, in->contact, in->phase, controls, in->foot_ref);
+  return check_common(h, B, *in, controls);
 }
 
 // the device entry: everything device-addressable, asynchronous on `stream`
@@ -782,7 +795,7 @@ int eval_host(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, con
   size_t bytes[N], off[N], tot = 0;                       // off, tot in doubles
   for (size_t i = 0; i < N; ++i) {
     const OutSlot& s = slots.s[i];
-    bytes[i] = s.p ? n * (s.fixed + s.per_step * H) * s.elem : 0;
+    bytes[i] = s.p ? n * s.w.bytes(H) : 0;
     off[i] = tot;
     tot += (bytes[i] + sizeof(double) - 1) / sizeof(double);
   }
@@ -948,30 +961,19 @@ int bmpc_create(bmpc_handle* out, const bmpc_params* params, int device, int max
 }
 
 int bmpc_destroy(bmpc_handle h) {
-  if (!h) return BMPC_OK;
+  if (!h) return BMPC_OK;                       // (bmpc_create's failure path comes here with some streams and events still null)
   (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  h->x_fb.release(); h->foot.release(); h->x_cmd.release(); h->mu.release(); h->controls.release();
-  h->states.release(); h->resid.release(); h->contact.release(); h->phase.release(); h->iters.release();
-  h->status.release(); h->nfactor.release(); h->dbg.release();
-  h->ll_q.release(); h->ll_qd.release(); h->ll_pf.release(); h->ll_u0.release(); h->ll_tau.release();
-  h->ll_t.release(); h->ll_c0.release();
-  h->warm.release(); h->ro_controls.release(); h->ro_states.release(); h->ro_contact.release();
-  h->ro_phase.release(); h->ro_iters.release(); h->ro_status.release(); h->ro_order.release();
-  for (int c = 0; c < bmpc_handle_s::HOST_CHUNKS; ++c) {
-    if (h->cstream[c]) { (void)hipStreamSynchronize(h->cstream[c]); (void)hipStreamDestroy(h->cstream[c]); }
-    if (h->cev[c]) (void)hipEventDestroy(h->cev[c]);
-  }
-  if (h->cev_own) (void)hipEventDestroy(h->cev_own);
-  if (h->cev_in) (void)hipEventDestroy(h->cev_in);
-  h->io_states.release();
-  h->x_ref.release(); h->foot_ref.release(); h->eval_out.release();
-  h->pin_in.release(); h->pin_out.release(); h->dev_in.release(); h->dev_out.release();
-  h->io_in.release(); h->io_out.release(); h->io_dev.release();
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  const hipStream_t streams[] = {h->stream, h->cstream[0], h->cstream[1], h->cstream[2]};
+  const hipEvent_t events[] = {h->cev[0], h->cev[1], h->cev[2], h->cev_own, h->cev_in, h->ev0, h->ev1};
+  static_assert(bmpc_handle_s::HOST_CHUNKS == 3, "one entry per chunk stream and event above");
+  // nothing is freed under a running copy or kernel: every stream of the handle is drained first
+  for (hipStream_t st : streams)
+    if (st) (void)hipStreamSynchronize(st);
+  delete h;                                     // every DevBuf / PinnedBuf / RetiringPinnedBuf member frees itself
+  for (hipEvent_t ev : events)
+    if (ev) (void)hipEventDestroy(ev);
+  for (hipStream_t st : streams)
+    if (st) (void)hipStreamDestroy(st);
   return BMPC_OK;
 }
 
@@ -1000,7 +1002,7 @@ int bmpc_solve_batch_device(bmpc_handle h, int B, const float* x_fb, const float
                             void* stream) {
   if (!h) return fail(BMPC_ERR_INVALID, "null handle");
   SolveIO io;
-  io.x_fb = x_fb; io.foot = foot; io.contact = contact; io.phase = phase; io.x_cmd = x_cmd; io.mu = mu;
+  io.in = {x_fb, foot, contact, phase, x_cmd, mu, nullptr, nullptr};
   io.controls = controls; io.states = states; io.iters = iters; io.resid = residuals; io.status = status; io.nfactor = nfactor;
   return solve_device_ordered(h, B, io, stream, h->order);
 }
@@ -1010,8 +1012,7 @@ int bmpc_solve_inputs_device(bmpc_handle h, int B, const bmpc_inputs* in, float*
   if (!h) return fail(BMPC_ERR_INVALID, "null handle");
   if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
   SolveIO io;
-  io.x_fb = in->x_fb; io.foot = in->foot; io.contact = in->contact; io.phase = in->phase; io.x_cmd = in->x_cmd; io.mu = in->mu;
-  io.x_ref = in->x_ref; io.foot_ref = in->foot_ref;
+  io.in = *in;
   io.controls = controls; io.states = states; io.iters = iters; io.resid = residuals; io.status = status; io.nfactor = nfactor;
   return solve_device_ordered(h, B, io, stream, h->order);
 }
@@ -1022,28 +1023,20 @@ int bmpc_host_io(bmpc_handle h, int B, int with_x_cmd, int with_mu, int with_sta
   HIP_TRY(hipSetDevice(h->device));
   bmpc_handle_s::IoLayout& L = h->io;
   // inputs | outputs, every array 64-byte aligned, fp64 controls and states; B = 0 (no layout) until the block is there
-  L = {packed_layout((size_t)B, (size_t)h->dev.h, with_x_cmd, with_mu, with_states, 64, 8)};
+  L = {packed_layout((size_t)B, (size_t)h->dev.h, (with_x_cmd ? 1u << I_XCMD : 0) | (with_mu ? 1u << I_MU : 0),
+                     with_states ? 1u << O_S : 0, 64, 8)};
   h->io_gen = h->io_gen == 0x7fffffff ? 1 : h->io_gen + 1;
   // (the handle's own stream may still read the old block: a re-allocation waits for it)
   if (L.in_bytes > h->io_in.n || L.out_bytes > h->io_out.n) HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(h->io_in.ensure(L.in_bytes));
   HIP_TRY(h->io_out.ensure(L.out_bytes));
   HIP_TRY(h->io_dev.ensure(L.in_bytes));
-  L.B = B; L.x_cmd = with_x_cmd != 0; L.mu = with_mu != 0; L.states = with_states != 0;
-  char* in = h->io_in.p;
-  char* o = h->io_out.p;
-  out->x_fb = reinterpret_cast<float*>(in + L.i_xfb);
-  out->foot = reinterpret_cast<float*>(in + L.i_foot);
-  out->phase = reinterpret_cast<int32_t*>(in + L.i_phase);
-  out->x_cmd = with_x_cmd ? reinterpret_cast<float*>(in + L.i_xcmd) : nullptr;
-  out->mu = with_mu ? reinterpret_cast<float*>(in + L.i_mu) : nullptr;
-  out->contact = reinterpret_cast<uint8_t*>(in + L.i_con);
-  out->controls = reinterpret_cast<double*>(o + L.o_u);
-  out->states = with_states ? reinterpret_cast<double*>(o + L.o_s) : nullptr;
-  out->iters = reinterpret_cast<int32_t*>(o + L.o_it);
-  out->status = reinterpret_cast<int32_t*>(o + L.o_st);
-  out->nfactor = reinterpret_cast<int32_t*>(o + L.o_nf);
-  out->residuals = reinterpret_cast<float*>(o + L.o_rs);
+  L.B = B;
+  *out = {};                                    // (an array the layout does not hold: a null view)
+  for (int i = 0; i < N_IN; ++i)
+    if (L.has_in >> i & 1) set_ptr(out, IN[i].view, h->io_in.p + L.in[i]);
+  for (int i = 0; i < N_OUT; ++i)
+    if (L.has_out >> i & 1) set_ptr(out, OUT[i].view, h->io_out.p + L.out[i]);
   return BMPC_OK;
 }
 
@@ -1065,8 +1058,9 @@ int bmpc_solve_batch_io(bmpc_handle h, int B) {
   // controls (and the per-instance counters) go straight from the kernels' epilogues into the host arrays -- free below that
   // rate --, the states are stored in HBM and follow by copy engine, chunk by chunk on the chunk streams of the host-pointer
   // path, so that only the last chunk's copy (15 % of the states) is exposed.  Everything through the kernels: +0.12 ms.
-  const ChunkPlan plan = plan_chunks(h, n, !L.states);     // (no states: one chunk, everything straight from the kernel)
-  if (L.states) HIP_TRY(h->io_states.ensure(n * H * 13));
+  const bool states = L.has_out >> O_S & 1;
+  const ChunkPlan plan = plan_chunks(h, n, !states);     // (no states: one chunk, everything straight from the kernel)
+  if (states) HIP_TRY(h->io_states.ensure(n * OUT[O_S].w.count(H)));
   HIP_TRY(chunks_after_own_stream(h, plan.n));
   int issued = 0;
   for (int c = 0; c < plan.n; ++c) {
@@ -1081,12 +1075,13 @@ int bmpc_solve_batch_io(bmpc_handle h, int B) {
     }
     // (the last chunk's states go the way of the controls: nothing is left to copy when its kernel ends, and 15 % of the
     //  states on top of the controls stay well below what the kernels' own stores sustain)
-    const bool by_copy = L.states && c < plan.n - 1;
-    SolveIO io = packed_io(L, din, o, lo, H, L.x_cmd, L.mu);
-    io.controls64 = reinterpret_cast<double*>(o + L.o_u) + lo * H * 12;
-    if (L.states) io.states64 = by_copy ? h->io_states.p + lo * H * 13 : reinterpret_cast<double*>(o + L.o_s) + lo * H * 13;
+    const bool by_copy = states && c < plan.n - 1;
+    SolveIO io = packed_io(L, din, o, lo);
+    io.controls64 = reinterpret_cast<double*>(o + L.out_at(O_U, lo));
+    double* states_host = reinterpret_cast<double*>(o + L.out_at(O_S, lo));
+    if (states) io.states64 = by_copy ? h->io_states.p + lo * OUT[O_S].w.count(H) : states_host;
     if (int rc = solve_device_ordered(h, (int)nb, io, st, h->order, plan.events(c)); rc != BMPC_OK) return bail(h, issued, rc);
-    if (by_copy) CHUNK_TRY(hipMemcpyAsync(reinterpret_cast<double*>(o + L.o_s) + lo * H * 13, io.states64, nb * H * 13 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (by_copy) CHUNK_TRY(hipMemcpyAsync(states_host, io.states64, nb * L.stride(OUT[O_S]), hipMemcpyDeviceToHost, st));
     CHUNK_TRY(hipEventRecord(h->cev[c], st));
   }
   for (int c = 0; c < plan.n; ++c) CHUNK_TRY(hipEventSynchronize(h->cev[c]));
@@ -1097,21 +1092,22 @@ int bmpc_solve_batch_io(bmpc_handle h, int B) {
 int bmpc_solve_batch(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
                      const int32_t* phase, const float* x_cmd, const float* mu, float* controls, float* states,
                      int32_t* iters, float* residuals, int32_t* status, int32_t* nfactor) {
-  return solve_host<float>(h, B, x_fb, foot, contact, phase, x_cmd, mu, controls, states, iters, residuals, status, nfactor);
+  const bmpc_inputs in = {x_fb, foot, contact, phase, x_cmd, mu, nullptr, nullptr};
+  return solve_host<float>(h, B, in, controls, states, iters, residuals, status, nfactor);
 }
 
 int bmpc_solve_batch_f64(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
                          const int32_t* phase, const float* x_cmd, const float* mu, double* controls, double* states,
                          int32_t* iters, float* residuals, int32_t* status, int32_t* nfactor) {
-  return solve_host<double>(h, B, x_fb, foot, contact, phase, x_cmd, mu, controls, states, iters, residuals, status, nfactor);
+  const bmpc_inputs in = {x_fb, foot, contact, phase, x_cmd, mu, nullptr, nullptr};
+  return solve_host<double>(h, B, in, controls, states, iters, residuals, status, nfactor);
 }
 
 int bmpc_solve_inputs_f64(bmpc_handle h, int B, const bmpc_inputs* in, double* controls, double* states, int32_t* iters,
                           float* residuals, int32_t* status, int32_t* nfactor) {
   if (!h) return fail(BMPC_ERR_INVALID, "null handle");
   if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
-  return solve_host<double>(h, B, in->x_fb, in->foot, in->contact, in->phase, in->x_cmd, in->mu, controls, states, iters, residuals,
-                            status, nfactor, in->x_ref, in->foot_ref);
+  return solve_host<double>(h, B, *in, controls, states, iters, residuals, status, nfactor);
 }
 
 int bmpc_synchronize(bmpc_handle h) {
@@ -1129,7 +1125,7 @@ int bmpc_debug_assemble_inputs(bmpc_handle h, int B, const bmpc_inputs* in, doub
   if (!h) return fail(BMPC_ERR_INVALID, "null handle");
   if (!in) return fail(BMPC_ERR_INVALID, "null bmpc_inputs");
   float dummy = 0;
-  if (int rc = check_common(h, B, in->x_fb, in->foot, in->contact, in->phase, &dummy, in->foot_ref); rc <= 0) return rc;
+  if (int rc = check_common(h, B, *in, &dummy); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B, H = (size_t)h->dev.h, NW = 6 * H;
   // only what the caller asked for is formed: Gt alone is n (6h)^2 doubles (1.9 GB at B = 4096, h = 40), and the Gt / qt
@@ -1145,8 +1141,8 @@ int bmpc_debug_assemble_inputs(bmpc_handle h, int B, const bmpc_inputs* in, doub
   if (int rc = stage_inputs(h, B, *in, nullptr, &din); rc != BMPC_OK) return rc;
   bmpc::DebugOut dbg = {h->dbg.p + o_xr, h->dbg.p + o_fr, Gt ? h->dbg.p + o_gt : nullptr, qt ? h->dbg.p + o_qt : nullptr, nullptr, 1};
   SolveIO io;
-  io.x_fb = din.x_fb; io.foot = din.foot; io.contact = din.contact; io.phase = din.phase; io.x_cmd = din.x_cmd; io.mu = din.mu;
-  io.x_ref = din.x_ref; io.foot_ref = din.foot_ref; io.controls = h->controls.p;
+  io.in = din;
+  io.controls = h->controls.p;
   if (int rc = launch(h, B, io, dbg, st, nullptr); rc != BMPC_OK) return rc;
   if (x_ref) HIP_TRY(hipMemcpyAsync(x_ref, h->dbg.p + o_xr, n * H * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
   if (foot_ref) HIP_TRY(hipMemcpyAsync(foot_ref, h->dbg.p + o_fr, n * H * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1213,17 +1209,17 @@ int bmpc_foot_position_world_device(bmpc_handle h, int B, const float* x_fb, con
 
 int bmpc_foot_position_world(bmpc_handle h, int B, const float* x_fb, const float* q, float* pf_w) {
   if (int rc = check_batch(h, B); rc <= 0) return rc;
-  if (!x_fb || !q || !pf_w) return fail(BMPC_ERR_INVALID, "null pointer");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B;
-  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->ll_q.ensure(n * 10)); HIP_TRY(h->ll_pf.ensure(n * 6));
-  hipStream_t st = h->stream;
-  HIP_TRY(hipMemcpyAsync(h->x_fb.p, x_fb, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->ll_q.p, q, n * 10 * sizeof(float), hipMemcpyHostToDevice, st));
-  int rc = bmpc_foot_position_world_device(h, B, h->x_fb.p, h->ll_q.p, h->ll_pf.p, st);
+  const float *d_x, *d_q;
+  int rc = upload(h, h->stage[I_XFB], x_fb, n * IN[I_XFB].w.count(0), &d_x);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_q, q, n * 10, &d_q);
   if (rc != BMPC_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(pf_w, h->ll_pf.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(h->ll_pf.ensure(n * 6));
+  rc = bmpc_foot_position_world_device(h, B, d_x, d_q, pf_w ? h->ll_pf.p : nullptr, h->stream);
+  if (rc != BMPC_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(pf_w, h->ll_pf.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return BMPC_OK;
 }
 
@@ -1243,25 +1239,23 @@ int bmpc_low_level_control_device(bmpc_handle h, int B, const float* x_fb, const
 int bmpc_low_level_control(bmpc_handle h, int B, const float* x_fb, const double* t, const float* pf_w,
                            const float* q, const float* qd, const uint8_t* contact0, const float* u0, float* tau) {
   if (int rc = check_batch(h, B); rc <= 0) return rc;
-  if (!x_fb || !t || !pf_w || !q || !qd || !contact0 || !u0 || !tau) return fail(BMPC_ERR_INVALID, "null pointer");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B;
-  HIP_TRY(h->x_fb.ensure(n * 12)); HIP_TRY(h->ll_t.ensure(n)); HIP_TRY(h->ll_pf.ensure(n * 6));
-  HIP_TRY(h->ll_q.ensure(n * 10)); HIP_TRY(h->ll_qd.ensure(n * 10)); HIP_TRY(h->ll_c0.ensure(n * 2));
-  HIP_TRY(h->ll_u0.ensure(n * 12)); HIP_TRY(h->ll_tau.ensure(n * 10));
-  hipStream_t st = h->stream;
-  HIP_TRY(hipMemcpyAsync(h->x_fb.p, x_fb, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->ll_t.p, t, n * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->ll_pf.p, pf_w, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->ll_q.p, q, n * 10 * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->ll_qd.p, qd, n * 10 * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->ll_c0.p, contact0, n * 2, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->ll_u0.p, u0, n * 12 * sizeof(float), hipMemcpyHostToDevice, st));
-  int rc = bmpc_low_level_control_device(h, B, h->x_fb.p, h->ll_t.p, h->ll_pf.p, h->ll_q.p, h->ll_qd.p, h->ll_c0.p,
-                                         h->ll_u0.p, h->ll_tau.p, st);
+  const float *d_x, *d_pf, *d_q, *d_qd, *d_u0;
+  const double* d_t; const uint8_t* d_c0;
+  int rc = upload(h, h->stage[I_XFB], x_fb, n * IN[I_XFB].w.count(0), &d_x);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_t, t, n, &d_t);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_pf, pf_w, n * 6, &d_pf);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_q, q, n * 10, &d_q);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_qd, qd, n * 10, &d_qd);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_c0, contact0, n * 2, &d_c0);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_u0, u0, n * 12, &d_u0);
   if (rc != BMPC_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(tau, h->ll_tau.p, n * 10 * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(h->ll_tau.ensure(n * 10));
+  rc = bmpc_low_level_control_device(h, B, d_x, d_t, d_pf, d_q, d_qd, d_c0, d_u0, tau ? h->ll_tau.p : nullptr, h->stream);
+  if (rc != BMPC_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(tau, h->ll_tau.p, n * 10 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return BMPC_OK;
 }
 
@@ -1302,17 +1296,19 @@ int bmpc_contact_sequence_device(bmpc_handle h, int B, const double* t, const bm
 
 int bmpc_contact_sequence(bmpc_handle h, int B, const double* t, const bmpc_gait* gait, int32_t* phase, uint8_t* contact) {
   if (int rc = check_batch(h, B); rc <= 0) return rc;
-  if (!t) return fail(BMPC_ERR_INVALID, "null pointer");
   HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B, hh = (size_t)h->params.h;
-  HIP_TRY(h->ll_t.ensure(n)); HIP_TRY(h->phase.ensure(n)); HIP_TRY(h->contact.ensure(n * hh * 2));
-  hipStream_t st = h->stream;
-  HIP_TRY(hipMemcpyAsync(h->ll_t.p, t, n * sizeof(double), hipMemcpyHostToDevice, st));
-  int rc = bmpc_contact_sequence_device(h, B, h->ll_t.p, gait, h->phase.p, h->contact.p, st);
+  const size_t n = (size_t)B, H = (size_t)h->params.h;
+  const double* d_t;
+  if (int rc = upload(h, h->ll_t, t, n, &d_t); rc != BMPC_OK) return rc;
+  DevBuf<char>&d_phase = h->stage[I_PHASE], &d_contact = h->stage[I_CON];
+  HIP_TRY(d_phase.ensure(n * IN[I_PHASE].w.bytes(H)));
+  HIP_TRY(d_contact.ensure(n * IN[I_CON].w.bytes(H)));
+  int rc = bmpc_contact_sequence_device(h, B, d_t, gait, reinterpret_cast<int32_t*>(d_phase.p), reinterpret_cast<uint8_t*>(d_contact.p),
+                                        h->stream);
   if (rc != BMPC_OK) return rc;
-  if (phase) HIP_TRY(hipMemcpyAsync(phase, h->phase.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (contact) HIP_TRY(hipMemcpyAsync(contact, h->contact.p, n * hh * 2, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (phase) HIP_TRY(hipMemcpyAsync(phase, d_phase.p, n * IN[I_PHASE].w.bytes(H), hipMemcpyDeviceToHost, h->stream));
+  if (contact) HIP_TRY(hipMemcpyAsync(contact, d_contact.p, n * IN[I_CON].w.bytes(H), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return BMPC_OK;
 }
 
@@ -1342,8 +1338,8 @@ int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const floa
   if (!x_fb || !foot || !t) return fail(BMPC_ERR_INVALID, "x_fb, foot and t must be non-null");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B, H = (size_t)h->dev.h;
-  HIP_TRY(h->ro_controls.ensure(n * H * 12)); HIP_TRY(h->ro_states.ensure(n * H * 13));
-  HIP_TRY(h->ro_contact.ensure(n * H * 2)); HIP_TRY(h->ro_phase.ensure(n));
+  HIP_TRY(h->ro_controls.ensure(n * OUT[O_U].w.count(H))); HIP_TRY(h->ro_states.ensure(n * OUT[O_S].w.count(H)));
+  HIP_TRY(h->ro_contact.ensure(n * IN[I_CON].w.count(H))); HIP_TRY(h->ro_phase.ensure(n));
   HIP_TRY(h->ro_iters.ensure(n)); HIP_TRY(h->ro_status.ensure(n));
   hipStream_t st = pick_stream(h, stream);
   if (status_any) HIP_TRY(hipMemsetAsync(status_any, 0, n * sizeof(int32_t), st));
@@ -1351,7 +1347,7 @@ int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const floa
   const bool own_order = h->longest_first && !order;
   if (own_order) HIP_TRY(h->ro_order.ensure(n));
   SolveIO io;
-  io.x_fb = x_fb; io.foot = foot; io.contact = h->ro_contact.p; io.phase = h->ro_phase.p; io.x_cmd = x_cmd; io.mu = mu;
+  io.in = {x_fb, foot, h->ro_contact.p, h->ro_phase.p, x_cmd, mu, nullptr, nullptr};
   io.controls = h->ro_controls.p; io.states = h->ro_states.p; io.iters = h->ro_iters.p; io.status = h->ro_status.p;
   int rc = BMPC_OK;
   for (int s = 0; s < steps && rc == BMPC_OK; ++s) {
