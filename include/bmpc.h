@@ -513,8 +513,11 @@ int bmpc_contact_sequence_device(bmpc_handle h, int B, const double* t, const bm
  * by the handle, and starts from the state the previous call left for the same batch index (same B), advanced by
  * `shift` horizon steps (0: the schedule phase did not move; 1: one control period later) and with the penalties
  * pulled back towards their initial value, rho0 (rho / rho0)^theta (theta in [0, 1]; 1 keeps them).  The first
- * call after enabling, after bmpc_reset_warm_start, or with another B starts cold.  The optimum is the same; only
- * the iteration count changes.  enable == 0 switches it off.
+ * call after enabling, after bmpc_reset_warm_start, or with another B starts cold; so does the first call after a
+ * bmpc_set_params that moved the handle to the other kernel family (the families keep different states), and an
+ * instance whose stored state is not finite (its previous solve failed) -- that instance alone.  The optimum is the
+ * same; only the iteration count changes.  enable == 0 switches it off.  A shift outside [0, h) or a theta outside
+ * [0, 1] (NaN included) is BMPC_ERR_INVALID, whatever `enable` is, and leaves the previous setting as it was.
  *
  * bmpc_rollout_device: `steps` closed-loop control periods of B instances on one stream, DEVICE pointers, no host
  * arithmetic and no synchronisation: per period  t -> (phase, contact) [bmpc_contact_sequence_device]  ->  solve

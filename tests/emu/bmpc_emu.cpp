@@ -256,6 +256,13 @@ bool inv3(const double* a, double* o) {
 extern "C" int bmpc_emu_threads(int h) { return h == 10 ? bmpc::Dims<10>::NT : (h == 16 ? bmpc::Dims<16>::NT : (h == 20 ? bmpc::Dims<20>::NT : -1)); }
 // doubles per instance of the warm-start buffer of the stage path
 extern "C" int bmpc_emu_stage_warm(int h) { return 5 * bmpc::stage_steps_per_lane(h) * bmpc::stage_waves(h) * 12 * 6; }
+// The addressing of the warm-start buffers, for the tests that build one by hand.  Stage family: [B][HS][12][6], HS >= h step
+// slots (those past h are phantoms).  Dense family: [B][NT][6], variable (row = 6 j + c, foot f) in lane Dims<H>::lane_of.
+extern "C" int bmpc_emu_stage_hs(int h) { return 5 * bmpc::stage_steps_per_lane(h) * bmpc::stage_waves(h); }
+extern "C" int bmpc_emu_lane_of(int h, int row, int f) {
+  if (row < 0 || row >= 6 * h || f < 0 || f > 1) return -1;
+  return h == 10 ? bmpc::Dims<10>::lane_of(row, f) : (h == 16 ? bmpc::Dims<16>::lane_of(row, f) : (h == 20 ? bmpc::Dims<20>::lane_of(row, f) : -1));
+}
 
 extern "C" int bmpc_emu_solve(const bmpc_params* p, int B, const float* x_fb, const float* foot, const uint8_t* contact,
                               const int32_t* phase, const float* x_cmd, const float* mu, float* controls, float* states,

@@ -27,15 +27,42 @@ def threads(h):
     return int(lib.bmpc_emu_threads(int(h)))
 
 
+def warm_buffer(cparams, B, fill=np.nan):
+    """A warm-start buffer of the shape the kernel family of `cparams` addresses, every entry `fill`: dense (B, NT, 6) -- one
+    lane per slot --, stage (B, HS, 12, 6) -- step slot, state coordinate n = 2 c + f."""
+    lib = C.CDLL(build())
+    h = int(cparams.h)
+    if int(cparams.path) == 2:
+        return np.full((B, int(lib.bmpc_emu_stage_hs(h)), 12, 6), fill, np.float64)
+    return np.full((B, threads(h), 6), fill, np.float64)
+
+
+def warm_slots(cparams):
+    """Where the buffer of `warm_buffer` keeps variable (step j, component c, foot f): an int array (h, 6, 2) of indices into the
+    buffer of one instance flattened to (slots, 6).  Slots no entry names belong to no variable (phantom steps, spare lanes)."""
+    lib = C.CDLL(build())
+    h = int(cparams.h)
+    idx = np.empty((h, 6, 2), np.int64)
+    for j in range(h):
+        for c in range(6):
+            for f in range(2):
+                idx[j, c, f] = (j * 12 + 2 * c + f) if int(cparams.path) == 2 else int(lib.bmpc_emu_lane_of(h, 6 * j + c, f))
+    assert idx.min() >= 0 and len(np.unique(idx)) == idx.size
+    return idx
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def solve(cparams, x_fb, foot, contact, phase, x_cmd=None, mu=None, assemble_only=False, warm=None, warm_load=False,
           warm_shift=0, warm_theta=0.5):
-    """Same marshalling as BatchSolver.solve / assemble.  Returns dict.  `warm`: None, or a float64 array
-    (B, threads(h), 6) that receives the final solver state and, with warm_load, provides the start."""
+    """Same marshalling as BatchSolver.solve / assemble.  Returns dict.  `warm`: None, or a float64 array of the shape
+    `warm_buffer` gives (dense: (B, threads(h), 6)) that receives the final solver state and, with warm_load, provides the start."""
     lib = C.CDLL(build())
+    if warm is not None:
+        need = warm_buffer(cparams, np.asarray(x_fb).reshape(-1, 12).shape[0], 0.0)
+        assert warm.dtype == np.float64 and warm.flags.c_contiguous and warm.size >= need.size, "warm: see warm_buffer"
     # the emulation takes the penalties as they are: the scaling of `penalty_mode` is the library's host arithmetic
     from biped_mpc_py_amd import _lib as _bl
     eff = (C.c_double * 5)()

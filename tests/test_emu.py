@@ -97,6 +97,103 @@ def test_warm_start_same_optimum_on_cpu():
     print("iterations: warm", o1["iters"][0], "cold", cold1["iters"][0])     # fewer on average, not for every instance
 
 
+_BITS = ("controls", "states", "iters", "nfactor", "residuals", "status")
+_warm_cases = {}
+
+
+def _warm_case(path, h, B, seed):
+    """Problem P (walking, commanded v_x), the buffer W its converged solve leaves, and P one state feedback later: solved once per
+    (family, h) and shared; nothing of it is modified afterwards (the solves below get copies of W)."""
+    key = (path, h)
+    if key not in _warm_cases:
+        import __graft_entry__ as ge
+        ge.build()
+        import biped_mpc_py_amd as bm
+        s = util.synth_batch(B, h, seed, gait="walking", vx_cmd=True)
+        mpc = bm.MPC()
+        mpc.h = h
+        cp = bm.pack_params(mpc, bm.Biped(), half=s["half"], solver_options=dict(path=path))
+        W = emu.warm_buffer(cp, B)
+        o0 = emu.solve(cp, s["x_fb"], s["foot"], s["contact"], s["phase"], x_cmd=s["x_cmd"], warm=W)
+        assert (o0["status"] == 0).all()
+        slots = emu.warm_slots(cp)
+        flat = W.reshape(B, -1, 6)
+        real = np.zeros(flat.shape[1], bool)
+        real[slots.reshape(-1)] = True
+        # the solve wrote every variable's slot; the stage family leaves the phantom steps alone (the dense one stores the clone
+        # lanes too: copies of the last row)
+        assert np.isfinite(flat[:, real]).all()
+        if path == 2:
+            assert np.isnan(flat[:, ~real]).all()
+        x1 = o0["states"][:, 0, :12].copy()
+        args = (cp, x1, s["foot"], s["contact"], s["phase"])
+        cold = emu.solve(*args, x_cmd=s["x_cmd"])
+        _warm_cases[key] = dict(cp=cp, s=s, W=W, o0=o0, slots=slots, real=real, args=args, kw=dict(x_cmd=s["x_cmd"]), cold=cold)
+    return _warm_cases[key]
+
+
+def _same_bits(a, b, where):
+    for k in _BITS:
+        assert np.array_equal(a[k], b[k]), (where, k)
+
+
+# (family, h, shift, instances, seed).  Two instances on the cheapest case of each family: the stride from one instance's block
+# to the next is part of the map.  h = 14 with shift 13: every step but the first clamps to the last; h = 9, 14, 26: phantom steps.
+_WARM_MAP = [(1, 10, 1, 2, 31), (1, 16, 3, 1, 32), (2, 9, 1, 2, 33), (2, 14, 13, 1, 34), (2, 26, 1, 1, 35)]
+
+
+@pytest.mark.parametrize("path,h,shift,B,seed", _WARM_MAP)
+def test_warm_load_index_map_on_cpu(path, h, shift, B, seed):
+    """The index map of the warm-start load, exactly.  On the CPU the buffer is the test's own array, so "variable (j, c, f)
+    starts from what step min(j + shift, h - 1) left" can be stated by building that buffer by hand: the kernel loading W with
+    `shift` and the kernel loading the hand-shifted W' with shift 0 must give the same bits -- controls, states, iterations,
+    factorisations, residuals.  A wrong lane or step, a clamp at another place, a stride of another variant each change what is
+    loaded and with it the path of the iteration.  (The addressing itself comes from the emulation library: `Dims<H>::lane_of`
+    for the dense family, [HS][12][6] for the stage family.)"""
+    w = _warm_case(path, h, B, seed)
+    slots, W = w["slots"], w["W"]
+    got = emu.solve(*w["args"], **w["kw"], warm=W.copy(), warm_load=True, warm_shift=shift, warm_theta=0.5)
+    Wp = W.copy()
+    src, dst = W.reshape(B, -1, 6), Wp.reshape(B, -1, 6)
+    for j in range(h):
+        dst[:, slots[j].reshape(-1)] = src[:, slots[min(j + shift, h - 1)].reshape(-1)]
+    assert not np.array_equal(Wp, W, equal_nan=True)              # (the shift moves something: the case can fail)
+    want = emu.solve(*w["args"], **w["kw"], warm=Wp, warm_load=True, warm_shift=0, warm_theta=0.5)
+    assert (got["status"] == 0).all()
+    _same_bits(got, want, "shift %d against the hand-shifted buffer" % shift)
+    # and it is a warm start at all: another path than the cold solve's
+    cold = w["cold"]
+    assert not np.array_equal(got["iters"], cold["iters"]) or not np.array_equal(got["controls"], cold["controls"])
+    assert util.rel_err(got["controls"].astype(float), cold["controls"].astype(float)).max() <= util.REL_TOL
+
+
+@pytest.mark.parametrize("path,h,shift,B,seed", _WARM_MAP)
+def test_warm_load_reads_no_slot_without_a_variable_on_cpu(path, h, shift, B, seed):
+    """Slots of the buffer that hold no variable -- the phantom steps past h of the stage family, the spare lanes of the dense
+    family's workgroup -- are never read: NaN in them changes no bit (one NaN that is read makes the kernel drop the whole
+    state and start cold), and the stored state of a converged solve is a fixed point: started from it with the penalties kept
+    (shift 0, theta 1) the solve leaves at its first stopping test with the one factorisation it started with."""
+    w = _warm_case(path, h, B, seed)
+    W, spare = w["W"], ~w["real"]
+    if spare.any():                            # (dense h = 16: 192 lanes for 96 rows, no spare lane)
+        # the baseline holds a state that passes for one in those slots (a copy of a real slot): were they read, the baseline would
+        # start warm from it and the poisoned buffer cold
+        base, Wn = W.copy(), W.copy()
+        base.reshape(B, -1, 6)[:, spare] = W.reshape(B, -1, 6)[:, w["slots"][h - 1, 0, 0]][:, None]
+        Wn.reshape(B, -1, 6)[:, spare] = np.nan
+        a = emu.solve(*w["args"], **w["kw"], warm=Wn, warm_load=True, warm_shift=shift, warm_theta=0.5)
+        b = emu.solve(*w["args"], **w["kw"], warm=base, warm_load=True, warm_shift=shift, warm_theta=0.5)
+        _same_bits(a, b, "NaN in the slots without a variable")
+        assert not np.array_equal(a["iters"], w["cold"]["iters"]) or not np.array_equal(a["controls"], w["cold"]["controls"])   # (warm, both)
+    s = w["s"]
+    again = emu.solve(w["cp"], s["x_fb"], s["foot"], s["contact"], s["phase"], **w["kw"], warm=W.copy(), warm_load=True,
+                      warm_shift=0, warm_theta=1.0)
+    print("fixed point h=%d path %d: iters %s nfactor %s (first solve %s)" % (h, path, again["iters"], again["nfactor"], w["o0"]["iters"]))
+    assert (again["status"] == 0).all()
+    assert (again["iters"] == w["cp"].check_every).all() and (again["nfactor"] == 1).all()
+    assert util.rel_err(again["controls"].astype(float), w["o0"]["controls"].astype(float)).max() <= util.REL_TOL
+
+
 def test_no_lds_hand_over_without_a_barrier(tmp_path):
     """The emulation under ThreadSanitizer (tests/emu/tsan.py): lanes synchronise only where the GPU does (workgroup
     barrier, pair exchange, wave reduction), so an LDS value handed from one lane to another without an s_barrier in
