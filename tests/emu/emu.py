@@ -1,6 +1,6 @@
-"""ctypes driver of tests/emu/bmpc_emu.cpp (TEST INFRASTRUCTURE): the solve kernel's source executed on the CPU,
-one thread per lane.  Builds the shared object on first use (host clang from ROCm: the kernel source uses clang
-vector extensions)."""
+"""ctypes driver of tests/emu/bmpc_emu.cpp (TEST INFRASTRUCTURE): the kernels' sources executed on the CPU, one thread per
+lane -- both solve families here, the evaluation family in emu_eval.py, all in one shared library.  Builds it on first use
+(host clang from ROCm: the kernel source uses clang vector extensions)."""
 import ctypes as C
 import os
 import subprocess
@@ -15,7 +15,7 @@ CLANG = os.environ.get("BMPC_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
 
 def build(force=False):
     from biped_mpc_py_amd.synth import kernel_source_paths
-    srcs = [os.path.join(HERE, "bmpc_emu.cpp")] + kernel_source_paths()
+    srcs = [os.path.join(HERE, "bmpc_emu.cpp"), os.path.join(HERE, "bmpc_emu_harness.hpp")] + kernel_source_paths()
     if force or not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in srcs):
         subprocess.check_call([CLANG, "-std=c++20", "-O1", "-pthread", "-fPIC", "-shared", "-D_GNU_SOURCE",
                                "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-x", "c++", srcs[0], "-o", SO])
@@ -52,43 +52,63 @@ def warm_slots(cparams):
 
 
 def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return None if a is None else a.ctypes.data
+
+
+def inputs(h, x_fb, foot, contact, phase, x_cmd=None, mu=None, x_ref=None, foot_ref=None, controls=None):
+    """The arrays of a solve or an evaluation as the `BatchSolver` methods marshal them: (B, arrays by name -- contiguous, of the
+    ABI's dtypes, None where absent --, the `bmpc_inputs` descriptor over them).  The arrays have to outlive the descriptor's use."""
+    from biped_mpc_py_amd import _lib as _bl
+    f32 = lambda a, shp: None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).reshape(shp))
+    x_fb = f32(x_fb, (-1, 12))
+    B = x_fb.shape[0]
+    a = dict(x_fb=x_fb, foot=f32(foot, (B, 6)), contact=np.ascontiguousarray(np.asarray(contact).reshape(B, h, 2).astype(np.uint8)),
+             phase=np.ascontiguousarray(np.asarray(phase, np.int32).reshape(B)), x_cmd=f32(x_cmd, (B, 12)), mu=f32(mu, (B, h, 2)),
+             x_ref=f32(x_ref, (B, h, 12)), foot_ref=f32(foot_ref, (B, h, 6)), controls=f32(controls, (B, h, 12)))
+    desc = _bl.CInputs(*[_ptr(a[k]) for k in ("x_fb", "foot", "contact", "phase", "x_cmd", "mu", "x_ref", "foot_ref")])
+    return B, a, desc
+
+
+class _Out(C.Structure):                         # bmpc_emu_out
+    _fields_ = [(k, C.c_void_p) for k in ("controls", "states", "iters", "residuals", "status", "nfactor", "x_ref", "foot_ref", "Gt", "qt")]
+
+
+class _Warm(C.Structure):                        # bmpc_emu_warm
+    _fields_ = [("buf", C.c_void_p), ("load", C.c_int), ("store", C.c_int), ("shift", C.c_int), ("theta", C.c_double)]
+
+
+def dev_params(cparams):
+    """What the library's own `make_dev_params`, compiled into the emulation from the same header, resolves `cparams` to: (the
+    bytes of the `bmpc::DevParams`, the five penalties as `bmpc_effective_penalties` reports them); RuntimeError with the library's
+    message where it refuses the block."""
+    lib = C.CDLL(build())
+    buf, eff = C.create_string_buffer(4096), (C.c_double * 5)()
+    n = lib.bmpc_emu_dev_params(C.byref(cparams), buf, len(buf), eff)
+    if n <= 0:
+        lib.bmpc_emu_last_error.restype = C.c_char_p
+        raise RuntimeError(lib.bmpc_emu_last_error().decode())
+    return buf.raw[:n], list(eff)
 
 
 def solve(cparams, x_fb, foot, contact, phase, x_cmd=None, mu=None, assemble_only=False, warm=None, warm_load=False,
-          warm_shift=0, warm_theta=0.5):
-    """Same marshalling as BatchSolver.solve / assemble.  Returns dict.  `warm`: None, or a float64 array of the shape
-    `warm_buffer` gives (dense: (B, threads(h), 6)) that receives the final solver state and, with warm_load, provides the start."""
+          warm_shift=0, warm_theta=0.5, x_ref=None, foot_ref=None):
+    """Same marshalling as BatchSolver.solve / assemble; x_ref (B,h,12) / foot_ref (B,h,6) in the kernel layout, or None
+    (generated).  Returns dict.  `warm`: None, or a float64 array of the shape `warm_buffer` gives (dense: (B, threads(h), 6)) that
+    receives the final solver state and, with warm_load, provides the start."""
     lib = C.CDLL(build())
-    if warm is not None:
-        need = warm_buffer(cparams, np.asarray(x_fb).reshape(-1, 12).shape[0], 0.0)
-        assert warm.dtype == np.float64 and warm.flags.c_contiguous and warm.size >= need.size, "warm: see warm_buffer"
-    # the emulation takes the penalties as they are: the scaling of `penalty_mode` is the library's host arithmetic
-    from biped_mpc_py_amd import _lib as _bl
-    eff = (C.c_double * 5)()
-    _bl.check(_bl.load().bmpc_effective_penalties(C.byref(cparams), eff))
-    cp2 = type(cparams)()
-    C.memmove(C.byref(cp2), C.byref(cparams), C.sizeof(cparams))
-    cp2.rho, cp2.rho_eq_scale, cp2.rho_lo, cp2.rho_hi_f, cp2.rho_hi_m, cp2.penalty_mode = eff[0], eff[1] / eff[0], eff[2], eff[3], eff[4], 1
-    cparams = cp2
     h = int(cparams.h)
-    x_fb = np.ascontiguousarray(np.asarray(x_fb, np.float32).reshape(-1, 12))
-    B = x_fb.shape[0]
-    foot = np.ascontiguousarray(np.asarray(foot, np.float32).reshape(B, 6))
-    contact = np.ascontiguousarray(np.asarray(contact).reshape(B, h, 2).astype(np.uint8))
-    phase = np.ascontiguousarray(np.asarray(phase, np.int32).reshape(B))
-    x_cmd = None if x_cmd is None else np.ascontiguousarray(np.asarray(x_cmd, np.float32).reshape(B, 12))
-    mu = None if mu is None else np.ascontiguousarray(np.asarray(mu, np.float32).reshape(B, h, 2))
+    B, _keep, inp = inputs(h, x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref)
+    if warm is not None:
+        need = warm_buffer(cparams, B, 0.0)
+        assert warm.dtype == np.float64 and warm.flags.c_contiguous and warm.size >= need.size, "warm: see warm_buffer"
     out = dict(controls=np.zeros((B, h, 12), np.float32), states=np.zeros((B, h, 13), np.float32),
                iters=np.zeros(B, np.int32), residuals=np.zeros((B, 2), np.float32), status=np.zeros(B, np.int32),
                nfactor=np.zeros(B, np.int32), x_ref=np.zeros((B, h, 12)), foot_ref=np.zeros((B, h, 6)),
                Gt=np.zeros((B, 6 * h, 6 * h)), qt=np.zeros((B, 6 * h)))
-    lib.bmpc_emu_solve.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 16 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double]
-    rc = lib.bmpc_emu_solve(C.byref(cparams), B, _ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu),
-                            _ptr(out["controls"]), _ptr(out["states"]), _ptr(out["iters"]), _ptr(out["residuals"]),
-                            _ptr(out["status"]), _ptr(out["nfactor"]), _ptr(out["x_ref"]), _ptr(out["foot_ref"]),
-                            _ptr(out["Gt"]), _ptr(out["qt"]), 1 if assemble_only else 0,
-                            _ptr(warm), 1 if warm_load else 0, 0 if warm is None else 1, int(warm_shift), float(warm_theta))
-    if rc != 0:
-        raise RuntimeError("bmpc_emu_solve failed")
+    w = _Warm(_ptr(warm), 1 if warm_load else 0, 0 if warm is None else 1, int(warm_shift), float(warm_theta))
+    lib.bmpc_emu_solve.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    if lib.bmpc_emu_solve(C.byref(cparams), B, C.byref(inp), C.byref(_Out(**{k: _ptr(v) for k, v in out.items()})),
+                          1 if assemble_only else 0, C.byref(w)) != 0:
+        lib.bmpc_emu_last_error.restype = C.c_char_p
+        raise RuntimeError("bmpc_emu_solve failed: " + lib.bmpc_emu_last_error().decode())
     return out

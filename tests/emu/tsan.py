@@ -39,7 +39,7 @@ def races(stderr):
             if m:                               # innermost frame that carries a line number (a lambda's may not)
                 mm = None
                 for fr in lines[i + 1:i + 4]:
-                    mm = mm or re.search(r"(bmpc_kernels\.hip|bmpc_model\.hip|bmpc_emu\.cpp):(\d+)", fr)
+                    mm = mm or re.search(r"(bmpc_kernels\.hip|bmpc_model\.hip|bmpc_emu\.cpp|bmpc_emu_harness\.hpp):(\d+)", fr)
                 acc.append((m.group(1), mm.group(0) if mm else "?"))
         out.append(acc)
     return out

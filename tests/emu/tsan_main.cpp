@@ -1,4 +1,4 @@
-// tests/emu/tsan_main.cpp -- TEST INFRASTRUCTURE: runs the CPU emulation of the solve kernel (bmpc_emu.cpp) under
+// tests/emu/tsan_main.cpp -- TEST INFRASTRUCTURE: runs the CPU emulation of the solve kernel (bmpc_emu.cpp, bmpc_emu_harness.hpp) under
 // ThreadSanitizer.  The emulation synchronises lanes only where the GPU does (workgroup barrier = std::barrier, pair
 // exchange = a two-lane rendezvous, wave reduction = a 64-lane barrier), so an LDS hand-over between lanes that no
 // s_barrier orders shows up as a data race on the shared-memory image.  Input: a dump written by tests/emu/tsan.py.
@@ -25,9 +25,9 @@ int main(int argc, char** argv) {
   if (!ok) return 2;
   std::vector<float> controls(B * h * 12), states(B * h * 13), resid(B * 2);
   std::vector<int32_t> iters(B), status(B), nfac(B);
-  const int rc = bmpc_emu_solve(&p, B, x_fb.data(), foot.data(), contact.data(), phase.data(), x_cmd.data(), has_mu ? mu.data() : nullptr,
-                                controls.data(), states.data(), iters.data(), resid.data(), status.data(), nfac.data(), nullptr,
-                                nullptr, nullptr, nullptr, 0, nullptr, 0, 0, 0, 0.5);
+  const bmpc_inputs in = {x_fb.data(), foot.data(), contact.data(), phase.data(), x_cmd.data(), has_mu ? mu.data() : nullptr, nullptr, nullptr};
+  const bmpc_emu_out out = {controls.data(), states.data(), iters.data(), resid.data(), status.data(), nfac.data(), nullptr, nullptr, nullptr, nullptr};
+  const int rc = bmpc_emu_solve(&p, B, &in, &out, 0, nullptr);
   for (int b = 0; b < B; ++b) std::printf("instance %d: iters %d status %d nfactor %d u0[2] %.6f\n", b, iters[b], status[b], nfac[b], controls[b * h * 12 + 2]);
   return rc;
 }

@@ -1,5 +1,5 @@
 """KKT certificate of given controls (include/bmpc.h `bmpc_certify*`) without a GPU: the kernel's source run on the CPU
-(tests/emu/bmpc_emu_eval.cpp) against the yardstick of tests/certify_cases.py (the oracle's matrices and SciPy's NNLS, read from
+(tests/emu/bmpc_emu.cpp) against the yardstick of tests/certify_cases.py (the oracle's matrices and SciPy's NNLS, read from
 tests/golden/certify.npz), against the merged evaluation and gradient, the C ABI's struct and argument checks, and the Python
 surface."""
 import ctypes as C

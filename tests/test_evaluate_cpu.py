@@ -1,4 +1,4 @@
-"""Evaluation of given controls (include/bmpc.h ABI 13) without a GPU: the kernel's source run on the CPU (tests/emu/bmpc_emu_eval.cpp)
+"""Evaluation of given controls (include/bmpc.h ABI 13) without a GPU: the kernel's source run on the CPU (tests/emu/bmpc_emu.cpp)
 against the oracle's matrices (tests/eval_cases.py `yardstick`), the C ABI's struct and argument checks, and the Python surface."""
 import ctypes as C
 import os

@@ -1,5 +1,5 @@
 """Gradient of the evaluated cost (include/bmpc.h `bmpc_evaluate_grad*`) without a GPU: the kernel's source run on the CPU
-(tests/emu/bmpc_emu_eval.cpp) against the oracle's matrices (tests/eval_grad_cases.py `yardstick`) and against the merged
+(tests/emu/bmpc_emu.cpp) against the oracle's matrices (tests/eval_grad_cases.py `yardstick`) and against the merged
 evaluation, the C ABI's struct and argument checks, and the Python surface."""
 import ctypes as C
 import os

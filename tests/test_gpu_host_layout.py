@@ -3,7 +3,10 @@ C side's field table: which arrays there are, in which order, how wide, on which
 import ctypes as C
 import itertools
 
+import numpy as np
 import pytest
+
+from tests import util
 
 # (view, elements per instance as a function of h, bytes per element, the with_* flag it depends on or None), in block order
 INPUTS = (("x_fb", lambda h: 12, 4, None), ("foot", lambda h: 6, 4, None), ("phase", lambda h: 1, 4, None),
@@ -56,3 +59,28 @@ def test_io_block_layout():
             out_lo, out_hi = a["controls"], a["residuals"] + B * 2 * 4
             assert in_hi <= out_lo or out_hi <= in_lo, where
         sol.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path,h", [(1, 10), (2, 26)])               # dense h = 10; stage h = 26, the smallest two-wave variant
+def test_absolute_round_trip_solves_alike(path, h):
+    """The block with penalty_mode ABSOLUTE and the five numbers of `bmpc_effective_penalties` written back
+    (tests/test_host_logic.py: it resolves to the same kernel parameters) solves bit for bit like the SCALED block it came from:
+    8 walking instances at Q x 10, each block on a fresh handle."""
+    import biped_mpc_py_amd as bm
+    from biped_mpc_py_amd import _lib
+    B = 8
+    s = util.synth_batch(B, h, 7, gait="walking", vx_cmd=True)
+    cp = util.case_params(util.WEIGHT_CASES["Q_x10"], h, path)
+    cp.half = s["half"]
+    eff = (C.c_double * 5)()
+    _lib.check(_lib.load().bmpc_effective_penalties(C.byref(cp), eff))
+    got = []
+    for block in (cp, util.absolute_round_trip(cp, list(eff))):
+        sol = bm.BatchSolver(cparams=block, max_batch=B)
+        assert sol._lib.bmpc_solver_path(sol._h) == path
+        x, u, info = sol.solve(s["x_fb"], s["foot"], s["contact"], s["phase"], x_cmd=s["x_cmd"])
+        got.append(dict(controls=u, states=x, **{k: info[k] for k in ("iters", "nfactor", "status", "residuals")}))
+        sol.close()
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k

@@ -423,15 +423,7 @@ def test_non_default_weights_and_bounds(what):
     force cap is lowered until it binds in double support.  Against the oracle with the same parameters."""
     import biped_mpc_py_amd as bm
     B = 12
-    mods = {
-        "Q_x10": (lambda m: setattr(m, "Q", np.asarray(m.Q, float) * 10.0), None),
-        "Q_div10": (lambda m: setattr(m, "Q", np.asarray(m.Q, float) / 10.0), None),
-        "R_x10": (lambda m: setattr(m, "R", np.asarray(m.R, float) * 10.0), None),
-        "R_div10": (lambda m: setattr(m, "R", np.asarray(m.R, float) / 10.0), None),
-        "R_mixed": (lambda m: setattr(m, "R", np.asarray(m.R, float) * np.array([1, 3, 10, 1, 3, 10, 30, 1, 3, 30, 1, 3.0])), None),
-        "f_max_150": (None, lambda b: setattr(b, "f_max", np.array([[150.0], [150.0], [55.0]]))),
-    }
-    mpc_mod, biped_mod = mods[what]
+    mpc_mod, biped_mod = util.WEIGHT_CASES[what]
     for gait, seed, kw in (("standing", 41, {}), ("walking", 42, dict(vx_cmd=True))):
         s = util.synth_batch(B, 10, seed, gait=gait, **kw)
         mpc, biped = bm.MPC(), bm.Biped()
@@ -1283,21 +1275,7 @@ def test_stage_path_warm_start_and_rollout():
 # ------------------------------------------------------------------------------------------------------------------
 # the penalty schedule is scale-free -- weights, step length, mass, inertia, geometry, gravity
 # ------------------------------------------------------------------------------------------------------------------
-_NONDIAG_I = np.array([[0.932, 0.05, -0.03], [0.05, 0.942, 0.02], [-0.03, 0.02, 0.0711]])
-_PARAM_CASES = {
-    "default": (None, None),
-    "R_div100": (lambda m: setattr(m, "R", np.asarray(m.R, float) / 100.0), None),
-    "R_x100": (lambda m: setattr(m, "R", np.asarray(m.R, float) * 100.0), None),
-    "Q_x100": (lambda m: setattr(m, "Q", np.asarray(m.Q, float) * 100.0), None),
-    "dt_0.02": (lambda m: setattr(m, "dt", 0.02), None),
-    "dt_0.05": (lambda m: setattr(m, "dt", 0.05), None),
-    "m_8": (None, lambda b: setattr(b, "m", 8.0)),
-    "m_20": (None, lambda b: setattr(b, "m", 20.0)),
-    "I_nondiagonal": (None, lambda b: setattr(b, "I", _NONDIAG_I.copy())),
-    "lt_lh": (None, lambda b: (setattr(b, "lt", 0.12), setattr(b, "lh", 0.07))),
-    "g_3.7": (None, lambda b: setattr(b, "g", 3.7)),
-    "kv_0.05": (lambda m: setattr(m, "kv", 0.05), None),
-}
+_PARAM_CASES = util.PARAM_CASES
 _param_iters = {}
 
 

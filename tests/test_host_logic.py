@@ -199,6 +199,58 @@ def test_rescue_mode_is_a_solver_option_with_default_auto():
     assert b"rescue" in _lib.load().bmpc_last_error()
 
 
+_BLOCK_CASES = {**util.PARAM_CASES, **util.WEIGHT_CASES}
+_BLOCK_SHAPES = [(1, 10), (1, 16), (1, 20), (2, 10), (2, 26), (2, 40)]           # (path: 1 dense, 2 stage; h)
+
+
+@pytest.mark.parametrize("what", list(_BLOCK_CASES))
+def test_absolute_round_trip_resolves_to_the_same_block(what):
+    """`bmpc_effective_penalties` "returns what a block resolves to" (include/bmpc.h), and the converse holds: the block with
+    penalty_mode ABSOLUTE and the five effective values written back (rho = e0, rho_eq_scale = e1 / e0, rho_lo, rho_hi_f,
+    rho_hi_m) resolves to the same `bmpc::DevParams`, byte for byte -- the five are fp32 values held in doubles, e0 (e1 / e0) is
+    within two double ulps of e1 and rounds back to the same float, and ABSOLUTE applies neither the ratios nor the cap.  Every
+    parameter case of the GPU parity tests, dense h = 10, 16, 20 and stage h = 10, 26, 40.  The block is resolved by
+    `make_dev_params` of csrc/bmpc_host_params.hpp as host clang compiles it into the emulation library; the five numbers equal
+    what the same header gives in libbmpc.so, where hipcc's host pass compiles it: the two round alike."""
+    import ctypes as C
+    import __graft_entry__ as ge
+    ge.build()
+    from biped_mpc_py_amd import _lib
+    from tests.emu import emu
+    for path, h in _BLOCK_SHAPES:
+        cp = util.case_params(_BLOCK_CASES[what], h, path)
+        assert cp.penalty_mode == 0                                   # BMPC_PENALTY_SCALED
+        dev, eff = emu.dev_params(cp)
+        back, eff_back = emu.dev_params(util.absolute_round_trip(cp, eff))
+        assert back == dev and eff_back == eff, (what, path, h)
+        lib5 = (C.c_double * 5)()
+        _lib.check(_lib.load().bmpc_effective_penalties(C.byref(cp), lib5))
+        assert list(lib5) == eff, (what, path, h)
+
+
+def test_refused_blocks_are_refused_alike():
+    """A block `make_dev_params` refuses is refused by the library and by the emulation with the same message."""
+    import ctypes as C
+    import biped_mpc_py_amd as bm
+    import __graft_entry__ as ge
+    ge.build()
+    from biped_mpc_py_amd import _lib
+    from tests.emu import emu
+
+    def singular(cp):
+        for i in range(9):
+            cp.I[i] = 0.0
+    for mod, word in ((lambda cp: setattr(cp, "rescue", 3), "rescue"), (singular, "singular"), (lambda cp: setattr(cp, "kappa", 1.0), "kappa")):
+        cp = bm.pack_params(bm.MPC(), bm.Biped())
+        mod(cp)
+        assert _lib.load().bmpc_effective_penalties(C.byref(cp), (C.c_double * 5)()) == -1
+        msg = _lib.load().bmpc_last_error().decode()
+        assert word in msg
+        with pytest.raises(RuntimeError) as e:
+            emu.dev_params(cp)
+        assert str(e.value) == msg
+
+
 def test_kernel_source_hash_covers_code_not_commentary():
     """synth.kernel_source_hash strips comments before hashing; that is only sound while no string literal of the kernel
     sources contains a comment opener."""

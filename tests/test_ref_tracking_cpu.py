@@ -1,5 +1,5 @@
 """Reference tracking without a GPU: the fixture (the reference's own solve_mpc with its generators replaced, tests/gen_ref_tracking.py)
-pinned to the oracle, the kernels' source run on the CPU with supplied references (tests/emu/bmpc_emu_refs.cpp), the C ABI's
+pinned to the oracle, the kernels' source run on the CPU with supplied references (tests/emu/bmpc_emu.cpp), the C ABI's
 `bmpc_inputs` descriptor and argument checks, and the Python layout conversion and checks."""
 import ctypes as C
 import os
@@ -87,14 +87,14 @@ def test_kernel_source_tracks_supplied_references_on_cpu(path, h, kinds):
     import __graft_entry__ as ge
     ge.build()
     import biped_mpc_py_amd as bm
-    from tests.emu import emu_refs
+    from tests.emu import emu
     d = _fix(h)
     idx = [int(np.flatnonzero(d["kind"] == k)[0]) for k in kinds]
     mpc = bm.MPC()
     mpc.h = h
     cp = bm.pack_params(mpc, bm.Biped(), half=int(d["half"]), solver_options=dict(path=path))
     xr, fr = bm.references_to_kernel_layout(d["x_ref"][idx], d["foot_ref"][idx], h)
-    o = emu_refs.solve(cp, d["x_fb"][idx], d["foot"][idx], d["contact"][idx], d["phase"][idx], x_cmd=d["x_cmd"][idx],
+    o = emu.solve(cp, d["x_fb"][idx], d["foot"][idx], d["contact"][idx], d["phase"][idx], x_cmd=d["x_cmd"][idx],
                        x_ref=xr, foot_ref=fr)
     assert (o["status"] == 0).all(), o["status"]
     assert util.rel_err(o["controls"].astype(float), d["controls"][idx]).max() <= util.REL_TOL
@@ -103,7 +103,7 @@ def test_kernel_source_tracks_supplied_references_on_cpu(path, h, kinds):
     # kind f: supplying the generators' own output changes nothing, bit for bit
     f = [k for k, i in enumerate(idx) if d["kind"][i] == "f"]
     if f:
-        g = emu_refs.solve(cp, d["x_fb"][idx][f], d["foot"][idx][f], d["contact"][idx][f], d["phase"][idx][f], x_cmd=d["x_cmd"][idx][f])
+        g = emu.solve(cp, d["x_fb"][idx][f], d["foot"][idx][f], d["contact"][idx][f], d["phase"][idx][f], x_cmd=d["x_cmd"][idx][f])
         for key in ("controls", "states", "iters", "nfactor", "status"):
             assert np.array_equal(o[key][f], g[key]), key
 
@@ -116,7 +116,7 @@ def test_stage_kernel_source_tracks_supplied_references_on_cpu(h, kinds):
     import __graft_entry__ as ge
     ge.build()
     import biped_mpc_py_amd as bm
-    from tests.emu import emu_refs
+    from tests.emu import emu
     rng = np.random.default_rng(7 + h)
     cases = [rc.make_case(k, h, rng) for k in kinds]
     mpc = bm.MPC()
@@ -124,7 +124,7 @@ def test_stage_kernel_source_tracks_supplied_references_on_cpu(h, kinds):
     cp = bm.pack_params(mpc, bm.Biped(), half=cases[0]["half"], solver_options=dict(path=2))
     st = lambda k: np.stack([c[k] for c in cases])
     xr, fr = bm.references_to_kernel_layout(st("x_ref"), st("foot_ref"), h)
-    o = emu_refs.solve(cp, st("x_fb"), st("foot"), st("contact"), st("phase"), x_cmd=st("x_cmd"), x_ref=xr, foot_ref=fr)
+    o = emu.solve(cp, st("x_fb"), st("foot"), st("contact"), st("phase"), x_cmd=st("x_cmd"), x_ref=xr, foot_ref=fr)
     ref = np.stack([rc.oracle_solve(c, h)[0] for c in cases])
     assert (o["status"] == 0).all(), o["status"]
     assert util.rel_err(o["controls"].astype(float), ref).max() <= util.REL_TOL
