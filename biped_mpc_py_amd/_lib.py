@@ -26,12 +26,21 @@ EXPORTS = (
     "bmpc_low_level_control", "bmpc_low_level_control_device",
     "bmpc_gait_default", "bmpc_contact_sequence", "bmpc_contact_sequence_device",
     "bmpc_set_warm_start", "bmpc_reset_warm_start", "bmpc_rollout_device", "bmpc_set_dispatch_order",
+    "bmpc_plant_default", "bmpc_plant_step", "bmpc_plant_step_device", "bmpc_simulate_device",
 )
 
 
 class CGait(C.Structure):
     """`bmpc_gait` of include/bmpc.h."""
     _fields_ = [("period", C.c_int32), ("offset", C.c_int32 * 2), ("duty", C.c_int32 * 2)]
+
+
+class CPlant(C.Structure):
+    """`bmpc_plant` of include/bmpc.h: integrator, substeps, foot moves and push window of the closed-loop simulation."""
+    _fields_ = [(n, C.c_int32) for n in ("integrator", "substeps", "move_feet", "push_from", "push_steps")]
+
+
+PLANT_INTEGRATORS = {"euler": 0, "rk4": 1}     # enum bmpc_plant_integrator
 
 
 class CHostViews(C.Structure):
@@ -167,6 +176,10 @@ def load():
     lib.bmpc_reset_warm_start.argtypes = [vp]
     lib.bmpc_set_dispatch_order.argtypes = [vp, vp, ip]
     lib.bmpc_rollout_device.argtypes = [vp, ip, ip, vp, vp, vp, C.POINTER(CGait), vp, vp, vp, vp, vp, vp, vp]
+    lib.bmpc_plant_default.argtypes = [C.POINTER(CPlant)]
+    lib.bmpc_plant_step.argtypes = [vp, ip, C.POINTER(CPlant)] + [vp] * 6
+    lib.bmpc_plant_step_device.argtypes = [vp, ip, C.POINTER(CPlant)] + [vp] * 7
+    lib.bmpc_simulate_device.argtypes = [vp, ip, ip, C.POINTER(CPlant), vp, vp, vp, C.POINTER(CGait)] + [vp] * 9
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name != "bmpc_last_error":

@@ -690,6 +690,95 @@ class BatchSolver:
             u0.data_ptr(), xt.data_ptr(), None if its is None else its.data_ptr(), st_any.data_ptr(), st))
         return dict(u0=u0, x=xt, iters=its, status_any=st_any)
 
+    # ---- the plant and the closed loop on it (bmpc_plant_step*, bmpc_simulate_device) ---------------
+    @staticmethod
+    def _plant(integrator, substeps, move_feet=True, push_from=0, push_steps=0):
+        """`bmpc_plant` from the keyword arguments; an unknown integrator name or a value the library would refuse is a ValueError."""
+        if integrator not in _lib.PLANT_INTEGRATORS:
+            raise ValueError(f"integrator must be one of {sorted(_lib.PLANT_INTEGRATORS)}, not {integrator!r}")
+        if not 1 <= int(substeps) <= 64:
+            raise ValueError(f"substeps must be in [1, 64], not {substeps}")
+        if int(push_from) < 0 or int(push_steps) < 0:
+            raise ValueError("push_from and push_steps must be >= 0")
+        return _lib.CPlant(_lib.PLANT_INTEGRATORS[integrator], int(substeps), 1 if move_feet else 0, int(push_from), int(push_steps))
+
+    def plant_step(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4):
+        """One control period of the plant -- the nonlinear single rigid body of include/bmpc.h, NOT the controller's linear model --
+        under held controls (`bmpc_plant_step`): x_fb (B,12), u0 (B,12) = [f1 f2 m1 m2], foot (B,6), contact0 (B,2) (a leg with bit 0
+        transmits nothing), wrench (B,6) = [F, M] in the world frame or None -> x_next (B,12) fp64.  A bad instance (non-finite input,
+        pitch at +-90 degrees) comes back all NaN."""
+        plant = self._plant(integrator, substeps)
+        a = np.asarray(x_fb, np.float32)
+        if a.ndim != 2 or a.shape[1] != 12:
+            raise ValueError(f"x_fb must have shape (B, 12), not {a.shape}")
+        B = a.shape[0]
+        arrs = [np.ascontiguousarray(a)]
+        for name, v, shp, dt in (("u0", u0, (B, 12), np.float32), ("foot", foot, (B, 6), np.float32),
+                                 ("contact0", contact0, (B, 2), None), ("wrench", wrench, (B, 6), np.float32)):
+            if v is None and name == "wrench":
+                arrs.append(None)
+                continue
+            v = np.asarray(v)
+            if v.shape != shp:
+                raise ValueError(f"{name} must have shape {shp}, not {v.shape}")
+            arrs.append(np.ascontiguousarray((v != 0).astype(np.uint8) if dt is None else v.astype(dt)))
+        out = np.empty((B, 12), np.float32)
+        _lib.check(self._lib.bmpc_plant_step(self._h, B, C.byref(plant), *[_ptr(v) for v in arrs], _ptr(out)))
+        return out.astype(np.float64)
+
+    def plant_step_device(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4, x_next=None, stream=None):
+        """`plant_step` on device tensors (`bmpc_plant_step_device`): float32 x_fb (B,12), u0 (B,12), foot (B,6), uint8 contact0 (B,2),
+        float32 wrench (B,6) or None -> x_next (B,12) float32 (allocated unless given).  Asynchronous on `stream` (default: torch's
+        current stream); nothing crosses PCIe."""
+        import torch
+        plant = self._plant(integrator, substeps)
+        dev = x_fb.device
+        if dev.type != "cuda" or dev.index != self.device:
+            raise ValueError(f"tensors must live on cuda:{self.device}")
+        if x_fb.dim() != 2:
+            raise ValueError("x_fb must have shape (B, 12)")
+        B = x_fb.shape[0]
+        if x_next is None:
+            x_next = torch.empty((B, 12), dtype=torch.float32, device=dev)
+        args = [_tensor_ptr(x_fb, torch.float32, (B, 12), dev), _tensor_ptr(u0, torch.float32, (B, 12), dev),
+                _tensor_ptr(foot, torch.float32, (B, 6), dev), _tensor_ptr(contact0, torch.uint8, (B, 2), dev),
+                _tensor_ptr(wrench, torch.float32, (B, 6), dev), _tensor_ptr(x_next, torch.float32, (B, 12), dev)]
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        _lib.check(self._lib.bmpc_plant_step_device(self._h, B, C.byref(plant), *args, st))
+        return x_next
+
+    def simulate_device(self, x_fb, foot, t, steps, x_cmd=None, mu=None, period=None, offset=None, duty=None, integrator="rk4",
+                        substeps=4, move_feet=True, push=None, push_from=0, push_steps=0, want_iters=True, stream=None):
+        """`steps` closed-loop control periods against the plant of `plant_step` (`bmpc_simulate_device`): `rollout_device`'s loop
+        with the rigid body in place of the controller's own prediction.  x_fb (B,12) float32, foot (B,6) float32 and t (B,) float64
+        are advanced IN PLACE (so `foot` must be writable): with `move_feet` a leg that lands gets the swing controller's foothold
+        target at the new state.  push (B,6) float32 = [F, M] (world frame) or None acts in periods push_from <= s < push_from +
+        push_steps.  Returns dict(u0 (steps,B,12), x (steps,B,12), foot (steps,B,6) -- the footholds after each period's update --,
+        iters (steps,B) | None, status_any (B,)).  Asynchronous on `stream` (default: torch's current stream)."""
+        import torch
+        plant = self._plant(integrator, substeps, move_feet, push_from, push_steps)
+        dev = x_fb.device
+        if dev.type != "cuda" or dev.index != self.device:
+            raise ValueError(f"tensors must live on cuda:{self.device}")
+        if x_fb.dim() != 2 or int(steps) < 0:
+            raise ValueError("x_fb must have shape (B, 12) and steps must be >= 0")
+        B, steps = x_fb.shape[0], int(steps)
+        args = [_tensor_ptr(x_fb, torch.float32, (B, 12), dev), _tensor_ptr(foot, torch.float32, (B, 6), dev),
+                _tensor_ptr(t, torch.float64, (B,), dev)]
+        opt = [_tensor_ptr(x_cmd, torch.float32, (B, 12), dev), _tensor_ptr(mu, torch.float32, (B, self.h, 2), dev),
+               _tensor_ptr(push, torch.float32, (B, 6), dev)]
+        gait = self._gait(period, offset, duty)
+        u0 = torch.empty((steps, B, 12), dtype=torch.float32, device=dev)
+        xt = torch.empty((steps, B, 12), dtype=torch.float32, device=dev)
+        ft = torch.empty((steps, B, 6), dtype=torch.float32, device=dev)
+        its = torch.empty((steps, B), dtype=torch.int32, device=dev) if want_iters else None
+        st_any = torch.zeros(B, dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        _lib.check(self._lib.bmpc_simulate_device(
+            self._h, B, steps, C.byref(plant), *args, None if gait is None else C.byref(gait), *opt,
+            u0.data_ptr(), xt.data_ptr(), ft.data_ptr(), None if its is None else its.data_ptr(), st_any.data_ptr(), st))
+        return dict(u0=u0, x=xt, foot=ft, iters=its, status_any=st_any)
+
     def last_kernel_ms(self):
         ms = C.c_float(-1.0)
         _lib.check(self._lib.bmpc_last_kernel_ms(self._h, C.byref(ms)))

@@ -4,6 +4,7 @@
 #include "bmpc_kernels.hip"
 #include "bmpc_stage.hip"
 #include "bmpc_lowlevel.hip"
+#include "bmpc_plant.hip"
 #include "bmpc_evaluate.hip"
 #include "bmpc_evaluate_grad.hip"
 #include "bmpc_certify.hip"
@@ -1095,13 +1096,13 @@ int bmpc_reset_warm_start(bmpc_handle h) {
   return BMPC_OK;
 }
 
-int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const float* foot, double* t,
-                        const bmpc_gait* gait, const float* x_cmd, const float* mu, float* u0_traj, float* x_traj,
-                        int32_t* iters_traj, int32_t* status_any, void* stream) {
-  if (int rc = check_batch(h, B); rc < 0) return rc;
-  if (steps < 0) return fail(BMPC_ERR_INVALID, "steps must be >= 0");
-  if (B == 0 || steps == 0) return BMPC_OK;
-  if (!x_fb || !foot || !t) return fail(BMPC_ERR_INVALID, "x_fb, foot and t must be non-null");
+// The closed loop bmpc_rollout_device and bmpc_simulate_device share: per period  t -> (phase, contact)  ->  dispatch order (from the
+// second period on, where the roll-out orders its own: the instances that iterated longest last period go first)  ->  solve  ->
+// `feedback(s, st)`, the launch that closes the loop and records period s -- the only difference between the two entries.  All on
+// one stream, no host arithmetic, no synchronisation; the ro_* scratch holds the solve's outputs.
+extern "C++" template <typename Feedback>
+static int closed_loop(bmpc_handle h, int B, int steps, const float* x_fb, const float* foot, double* t, const bmpc_gait* gait,
+                       const float* x_cmd, const float* mu, int32_t* status_any, void* stream, Feedback feedback) {
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)B, H = (size_t)h->dev.h;
   HIP_TRY(h->ro_controls.ensure(n * OUT[O_U].w.count(H))); HIP_TRY(h->ro_states.ensure(n * OUT[O_S].w.count(H)));
@@ -1117,8 +1118,6 @@ int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const floa
   io.controls = h->ro_controls.p; io.states = h->ro_states.p; io.iters = h->ro_iters.p; io.status = h->ro_status.p;
   int rc = BMPC_OK;
   for (int s = 0; s < steps && rc == BMPC_OK; ++s) {
-    // t -> (phase, contact) -> solve -> x_fb <- states[:, 0], t += dt: three launches on one stream, no host arithmetic
-    // (plus, from the second period on, the dispatch order: the instances that iterated longest last period go first)
     rc = bmpc_contact_sequence_device(h, B, t, gait, h->ro_phase.p, h->ro_contact.p, st);
     if (rc != BMPC_OK) break;
     if (own_order && s > 0) {
@@ -1128,13 +1127,120 @@ int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const floa
     }
     rc = solve_device_ordered(h, B, io, stream, order);
     if (rc != BMPC_OK) break;
-    hipLaunchKernelGGL(bmpc::rollout_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, (int)H, h->params.dt,
-                       h->ro_states.p, h->ro_controls.p, h->ro_iters.p, h->ro_status.p, x_fb, t,
-                       u0_traj ? u0_traj + (size_t)s * n * 12 : nullptr, x_traj ? x_traj + (size_t)s * n * 12 : nullptr,
-                       iters_traj ? iters_traj + (size_t)s * n : nullptr, status_any);
+    feedback(s, st);
     if (hipGetLastError() != hipSuccess) rc = fail(BMPC_ERR_HIP, "roll-out launch failed");
   }
   return rc;
+}
+
+int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const float* foot, double* t,
+                        const bmpc_gait* gait, const float* x_cmd, const float* mu, float* u0_traj, float* x_traj,
+                        int32_t* iters_traj, int32_t* status_any, void* stream) {
+  if (int rc = check_batch(h, B); rc < 0) return rc;
+  if (steps < 0) return fail(BMPC_ERR_INVALID, "steps must be >= 0");
+  if (B == 0 || steps == 0) return BMPC_OK;
+  if (!x_fb || !foot || !t) return fail(BMPC_ERR_INVALID, "x_fb, foot and t must be non-null");
+  const size_t n = (size_t)B;
+  // x_fb <- states[:, 0], t += dt
+  return closed_loop(h, B, steps, x_fb, foot, t, gait, x_cmd, mu, status_any, stream, [&](int s, hipStream_t st) {
+    hipLaunchKernelGGL(bmpc::rollout_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, (int)h->dev.h, h->params.dt,
+                       h->ro_states.p, h->ro_controls.p, h->ro_iters.p, h->ro_status.p, x_fb, t,
+                       u0_traj ? u0_traj + (size_t)s * n * 12 : nullptr, x_traj ? x_traj + (size_t)s * n * 12 : nullptr,
+                       iters_traj ? iters_traj + (size_t)s * n : nullptr, status_any);
+  });
+}
+
+// ---- the plant and the closed loop on it (bmpc_plant.hip)
+
+int bmpc_plant_default(bmpc_plant* p) {
+  if (!p) return fail(BMPC_ERR_INVALID, "null plant");
+  p->integrator = BMPC_PLANT_RK4; p->substeps = 4; p->move_feet = 1; p->push_from = 0; p->push_steps = 0;
+  return BMPC_OK;
+}
+
+// `plant` (null: the default) checked and resolved; host arithmetic only, before a handle or a device is looked at
+static int plant_opts(const bmpc_plant* plant, bmpc_plant* out) {
+  if (plant) *out = *plant;
+  else bmpc_plant_default(out);
+  if (out->integrator != BMPC_PLANT_EULER && out->integrator != BMPC_PLANT_RK4)
+    return fail(BMPC_ERR_INVALID, "unknown integrator %d", out->integrator);
+  if (out->substeps < 1 || out->substeps > bmpc::PLANT_MAX_SUBSTEPS)
+    return fail(BMPC_ERR_INVALID, "substeps %d outside [1, %d]", out->substeps, bmpc::PLANT_MAX_SUBSTEPS);
+  if (out->push_from < 0 || out->push_steps < 0) return fail(BMPC_ERR_INVALID, "push_from and push_steps must be >= 0");
+  return BMPC_OK;
+}
+
+static bmpc::PlantParams plant_params(bmpc_handle h) {
+  const bmpc_params& p = h->params;
+  bmpc::PlantParams q;
+  q.h = p.h; q.dt = p.dt; q.kv = p.kv; q.m = p.m; q.g = p.g;
+  q.cmd_x = p.x_cmd[3]; q.cmd_y = p.x_cmd[4];
+  for (int i = 0; i < 9; ++i) { q.Ib[i] = p.I[i]; q.Ibinv[i] = h->dev.Iinv[i]; }
+  return q;
+}
+
+int bmpc_plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
+                           const uint8_t* contact0, const float* wrench, float* x_next, void* stream) {
+  bmpc_plant o;
+  if (int rc = plant_opts(plant, &o); rc != BMPC_OK) return rc;
+  if (int rc = check_batch(h, B); rc <= 0) return rc;
+  if (!x_fb || !u0 || !foot || !contact0 || !x_next) return fail(BMPC_ERR_INVALID, "x_fb, u0, foot, contact0 and x_next must be non-null");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  hipLaunchKernelGGL(bmpc::plant_step_kernel, dim3((B + 255) / 256), dim3(256), 0, st, plant_params(h),
+                     bmpc::plant_scheme(h->params.dt, o.integrator, o.substeps), B, x_fb, u0, foot, contact0, wrench, x_next);
+  HIP_TRY(hipGetLastError());
+  return BMPC_OK;
+}
+
+// (staging: the buffers of the low-level host entries -- ll_pf holds foot positions there too; ll_q the wrench, ll_tau the result)
+int bmpc_plant_step(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
+                    const uint8_t* contact0, const float* wrench, float* x_next) {
+  bmpc_plant o;
+  if (int rc = plant_opts(plant, &o); rc != BMPC_OK) return rc;
+  if (int rc = check_batch(h, B); rc <= 0) return rc;
+  if (!x_fb || !u0 || !foot || !contact0 || !x_next) return fail(BMPC_ERR_INVALID, "x_fb, u0, foot, contact0 and x_next must be non-null");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t n = (size_t)B;
+  const float *d_x, *d_u0, *d_foot, *d_w;
+  const uint8_t* d_c0;
+  int rc = upload(h, h->stage[I_XFB], x_fb, n * IN[I_XFB].w.count(0), &d_x);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_u0, u0, n * 12, &d_u0);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_pf, foot, n * 6, &d_foot);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_c0, contact0, n * 2, &d_c0);
+  if (rc == BMPC_OK) rc = upload(h, h->ll_q, wrench, n * 6, &d_w);
+  if (rc != BMPC_OK) return rc;
+  HIP_TRY(h->ll_tau.ensure(n * 12));
+  rc = bmpc_plant_step_device(h, B, &o, d_x, d_u0, d_foot, d_c0, d_w, h->ll_tau.p, h->stream);
+  if (rc != BMPC_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(x_next, h->ll_tau.p, n * 12 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return BMPC_OK;
+}
+
+int bmpc_simulate_device(bmpc_handle h, int B, int steps, const bmpc_plant* plant, float* x_fb, float* foot, double* t,
+                         const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push, float* u0_traj,
+                         float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any, void* stream) {
+  bmpc_plant o;
+  if (int rc = plant_opts(plant, &o); rc != BMPC_OK) return rc;
+  if (int rc = check_batch(h, B); rc < 0) return rc;
+  if (steps < 0) return fail(BMPC_ERR_INVALID, "steps must be >= 0");
+  if (B == 0 || steps == 0) return BMPC_OK;
+  if (!x_fb || !foot || !t) return fail(BMPC_ERR_INVALID, "x_fb, foot and t must be non-null");
+  bmpc::GaitParams G;
+  if (int rc = gait_params(h, gait, &G); rc != BMPC_OK) return rc;
+  const size_t n = (size_t)B;
+  const bmpc::PlantParams P = plant_params(h);
+  const bmpc::PlantScheme S = bmpc::plant_scheme(h->params.dt, o.integrator, o.substeps);
+  const bmpc::PlantGait PG = {G.period, {G.offset[0], G.offset[1]}, {G.duty[0], G.duty[1]}, o.move_feet != 0};
+  return closed_loop(h, B, steps, x_fb, foot, t, gait, x_cmd, mu, status_any, stream, [&](int s, hipStream_t st) {
+    const bool push_on = push && s >= o.push_from && s - o.push_from < o.push_steps;
+    hipLaunchKernelGGL(bmpc::simulate_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, P, S, PG, B, h->ro_controls.p,
+                       h->ro_contact.p, h->ro_iters.p, h->ro_status.p, push_on ? push : nullptr, x_cmd, x_fb, foot, t,
+                       u0_traj ? u0_traj + (size_t)s * n * 12 : nullptr, x_traj ? x_traj + (size_t)s * n * 12 : nullptr,
+                       foot_traj ? foot_traj + (size_t)s * n * 6 : nullptr, iters_traj ? iters_traj + (size_t)s * n : nullptr,
+                       status_any);
+  });
 }
 
 int bmpc_set_dispatch_order(bmpc_handle h, const int32_t* order_dev, int longest_first_rollouts) {

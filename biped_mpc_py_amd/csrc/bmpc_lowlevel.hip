@@ -4,8 +4,13 @@
 // Closed-form trigonometry, one thread per instance, f64 arithmetic (a few hundred flops: the kernels are
 // bound by their ~200 B/instance of I/O), f32 I/O like the rest of the ABI.  Quirks kept: R' is used for
 // body->world and world->body alike (REF:423, 461, 465).
+#ifndef BMPC_LOWLEVEL_HIP
+#define BMPC_LOWLEVEL_HIP
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "bmpc_model.hip"
 
 namespace bmpc {
 
@@ -104,8 +109,8 @@ lowlevel_kernel(const LowLevelParams P, const int B, const float* __restrict__ x
   eul2rotm_d(x, R);
   const double Ts = P.dt * P.h / 2;                                    // REF:436-437
   const double ts = fmod(t[i], Ts) < 0 ? fmod(t[i], Ts) + Ts : fmod(t[i], Ts);
-  const double dx = x[3] + x[9] * 0.5 * P.h / 2 * P.dt + P.kv * (x[3] - P.x_cmd[3]);   // REF:428-431
-  const double dy0 = x[4] + x[10] * 0.5 * P.h / 2 * P.dt + P.kv * (x[4] - P.x_cmd[4]);
+  const double dx = foothold_target(x[3], x[9], P.h, P.dt, P.kv, P.x_cmd[3]);          // REF:428-431
+  const double dy0 = foothold_target(x[4], x[10], P.h, P.dt, P.kv, P.x_cmd[4]);
   const double dz = P.swing_height * sin(3.14159265358979323846 * ts / Ts);
 #pragma unroll
   for (int leg = 0; leg < 2; ++leg) {
@@ -188,11 +193,8 @@ gait_kernel(const GaitParams G, const int B, const double* __restrict__ t, int32
   if (phase) phase[i] = k;
   if (contact) {
     for (int n = 0; n < G.h; ++n)                                       // REF:58: rows k .. k+h-1
-      for (int g = 0; g < 2; ++g) {
-        int m = (k + n + G.offset[g]) % G.period;
-        if (m < 0) m += G.period;
-        contact[((size_t)i * G.h + n) * 2 + g] = m < G.duty[g] ? 1 : 0;
-      }
+      for (int g = 0; g < 2; ++g)
+        contact[((size_t)i * G.h + n) * 2 + g] = in_stance(k + n, G.offset[g], G.period, G.duty[g]) ? 1 : 0;
   }
 }
 
@@ -245,3 +247,4 @@ __global__ void __launch_bounds__(1024) dispatch_order_kernel(int B, const int32
 }
 
 }  // namespace bmpc
+#endif

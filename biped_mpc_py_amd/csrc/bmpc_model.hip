@@ -50,6 +50,22 @@ __device__ __forceinline__ void general_rows(float mu, const float* ey, const fl
   }
 }
 
+// One horizontal coordinate of the foothold a swing leg is steered to (REF:428-434, without the lateral 0.04 side): position p,
+// velocity v and command cmd of that coordinate.  The swing controller's `des` (bmpc_lowlevel.hip) and the landing rule of the
+// closed-loop simulation (bmpc_plant.hip).
+__device__ __forceinline__ double foothold_target(const double p, const double v, const double h, const double dt, const double kv,
+                                                  const double cmd) {
+  return p + v * 0.5 * h / 2 * dt + kv * (p - cmd);
+}
+
+// Leg in stance at schedule step `step` (REF:52-55 generalised): ((step + offset) mod period) < duty, with a non-negative
+// remainder.  The gait scheduler (bmpc_lowlevel.hip) and the landing rule of the closed-loop simulation (bmpc_plant.hip).
+__device__ __forceinline__ bool in_stance(const int step, const int offset, const int period, const int duty) {
+  int m = (step + offset) % period;
+  if (m < 0) m += period;
+  return m < duty;
+}
+
 // ---------------------------------------------------------------------------------------------------- the ADMM row rules
 //   One row with iterate z, dual y, penalty rho (irv = 1 / rho) and the row's value zt = (A x~) of this
 // iteration: relaxation, projection onto the row's set, and the dual step dy = rho (z_relaxed - z_new), which the caller

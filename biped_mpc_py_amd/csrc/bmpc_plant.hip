@@ -1,0 +1,299 @@
+// bmpc_plant.hip -- the plant of the closed-loop simulation (gfx950 / CDNA4): the NONLINEAR single rigid body, integrated over one
+// control period under held controls, and the feedback step that closes bmpc_simulate_device's loop on it.
+//   plant_step               the per-instance body: values in, values out (also plain C++ for tests/emu, BMPC_EMU)
+//   plant_step_kernel        one control period of B instances (bmpc_plant_step*)
+//   simulate_feedback_kernel one closed-loop period: integrate x_fb under controls[:, 0], advance t, move landing feet, record
+// State x = [e(3), p(3), w(3), v(3)], e = [roll, pitch, yaw], w and v in the world frame (REF:13).  Held over the period: the
+// controls u = [f1 f2 m1 m2], the feet r_0, r_1, the contact bits c_0, c_1 and an external wrench [F(3), M(3)] (world frame).
+//   R = Rz(e2) Ry(e1) Rx(e0) (REF:124-138),  I_w = R I_b R'
+//   e0' = (cos e2 wx + sin e2 wy) / cos e1,  e1' = -sin e2 wx + cos e2 wy,  e2' = wz + sin e1 e0'
+//   p' = v
+//   tau = sum_g c_g [(r_g - p) x f_g + m_g] + M,   w' = I_w^-1 (tau - w x I_w w)
+//   v' = (sum_g c_g f_g + F) / m + (0, 0, -g)
+// This is NOT the controller's model (REF:148-185): that one maps rates through Rot / R_inv of the reference attitude, has no
+// gyroscopic term and does not gate a leg by its contact bit.  A leg with contact bit 0 transmits nothing here.
+// Integration: n in [1, 64] substeps of dt / n, explicit Euler (every component from the old stage values: the form of
+// A = I + Ac dt, REF:183-184) or classical RK4.  fp64 arithmetic on fp32 I/O.  A non-finite input, or |cos e1| < 2^-22 at any
+// stage (the threshold of bmpc_evaluate.hip), makes the whole next state of that instance NaN; no other instance is touched.
+// One thread per instance, no LDS, every array statically indexed; the angular rate equation is solved in the body frame
+// with I_b^-1 from the parameter block.
+// The lever arms enter as tau = T0 - p x Fc with T0, Fc formed once per period (plant_held): the same torque, 27 values fewer
+// to keep in registers through the stages.
+#ifndef BMPC_PLANT_HIP
+#define BMPC_PLANT_HIP
+
+#ifndef BMPC_EMU
+#include <hip/hip_runtime.h>
+#endif
+#include <stdint.h>
+
+#include "bmpc_model.hip"
+
+namespace bmpc {
+
+constexpr int PLANT_EULER = 0, PLANT_RK4 = 1;
+constexpr int PLANT_MAX_SUBSTEPS = 64;
+
+struct PlantParams {
+  double h, dt, kv, m, g;                      // h: the horizon as the foothold target uses it (REF:429)
+  double cmd_x, cmd_y, Ib[9], Ibinv[9];        // cmd: the handle's x_cmd[3], x_cmd[4]
+};
+
+__device__ __forceinline__ bool plant_finite(const float v) { return fabsf(v) <= 3.402823466e+38f; }   // (false for NaN)
+
+// What the held inputs contribute, formed once per period: the contact-gated force Fc = sum_g c_g f_g, the torque about the
+// world origin T0 = sum_g c_g (r_g x f_g + m_g) + M (so that tau = T0 - p x Fc), and the acceleration a = (Fc + F) / m - g e_z.
+struct PlantHeld { double Fc[3], T0[3], a[3]; };
+
+__device__ __forceinline__ PlantHeld plant_held(const PlantParams& P, const float (&u)[12], const float (&r)[6], const double c0,
+                                                const double c1, const float (&w)[6]) {
+  const double c[2] = {c0, c1};
+  PlantHeld H;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { H.Fc[i] = 0.0; H.T0[i] = (double)w[3 + i]; }
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const double f[3] = {(double)u[3 * g], (double)u[3 * g + 1], (double)u[3 * g + 2]};
+    const double a[3] = {(double)r[3 * g], (double)r[3 * g + 1], (double)r[3 * g + 2]};
+    H.T0[0] += c[g] * (a[1] * f[2] - a[2] * f[1] + (double)u[6 + 3 * g]);
+    H.T0[1] += c[g] * (a[2] * f[0] - a[0] * f[2] + (double)u[7 + 3 * g]);
+    H.T0[2] += c[g] * (a[0] * f[1] - a[1] * f[0] + (double)u[8 + 3 * g]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) H.Fc[i] += c[g] * f[i];
+  }
+  H.a[0] = (H.Fc[0] + (double)w[0]) / P.m; H.a[1] = (H.Fc[1] + (double)w[1]) / P.m; H.a[2] = (H.Fc[2] + (double)w[2]) / P.m - P.g;
+  return H;
+}
+
+// The integration scheme of a period as the host resolves it (uniform values: kernel arguments, so that they sit in scalar
+// registers; formed per thread they would each hold a vector register pair through the stage loop).
+struct PlantScheme {
+  int substeps, stages;                        // stages: 1 explicit Euler, 4 classical RK4
+  double hs, hh, wsum, half2;                  // dt / substeps, hs / 2, the weight of the stage sum (hs or hs / 6), hs^2 / 2 (RK4) or 0
+};
+inline PlantScheme plant_scheme(const double dt, const int integrator, const int substeps) {
+  PlantScheme S;
+  const bool rk4 = integrator != PLANT_EULER;
+  S.substeps = substeps; S.stages = rk4 ? 4 : 1;
+  S.hs = dt / (double)substeps; S.hh = 0.5 * S.hs;
+  S.wsum = rk4 ? S.hs / 6.0 : S.hs;
+  S.half2 = rk4 ? 0.5 * S.hs * S.hs : 0.0;
+  return S;
+}
+
+// The rates that depend on the state: de = e', dw = w' at attitude es, angular velocity w0 + cj kw and position
+// p0 + cj (v0 + cprev a) -- both formed behind the sincos passes, where fewer values are alive (p' = v and v' = H.a need no
+// evaluation); dw may be kw.  Returns false where |cos e1| < 2^-22.
+__device__ __forceinline__ bool plant_rate(const PlantParams& P, const PlantHeld& H, const double (&es)[3], const double (&p0)[3],
+                                           const double (&v0)[3], const double cprev, const double (&w0)[3], const double cj,
+                                           const double (&kw)[3], double (&de)[3], double (&dw)[3]) {
+  // The three fp64 sincos through ONE inlined body: a rolled loop over a ring of six registers (no indexed array).  Written out
+  // three times the scheduler interleaves them, and their temporaries add up to more registers than the rest of the step.
+  // The ring starts as (e0, -, e1, -, e2, -); a pass takes the angle at its head, turns the ring by two and puts (sin, cos) at
+  // its tail, so that it ends as (sin e0, cos e0, sin e1, cos e1, sin e2, cos e2).
+  double s0 = es[0], k0 = 0.0, s1 = es[1], k1 = 0.0, s2 = es[2], k2 = 0.0;
+#pragma unroll 1
+  for (int q = 0; q < 3; ++q) {
+    double sn, cs;
+    sincos(s0, &sn, &cs);
+    s0 = s1; k0 = k1; s1 = s2; k1 = k2; s2 = sn; k2 = cs;
+  }
+  const double w[3] = {w0[0] + cj * kw[0], w0[1] + cj * kw[1], w0[2] + cj * kw[2]};
+  const double ps[3] = {p0[0] + cj * (v0[0] + cprev * H.a[0]), p0[1] + cj * (v0[1] + cprev * H.a[1]), p0[2] + cj * (v0[2] + cprev * H.a[2])};
+  const double wz0 = k2 * w[0] + s2 * w[1], wz1 = -s2 * w[0] + k2 * w[1];        // Rz' w: also the numerators of the Euler rates
+  const double e0d = wz0 / k1;
+  de[0] = e0d;
+  de[1] = wz1;
+  de[2] = w[2] + s1 * e0d;
+  const double tau[3] = {H.T0[0] - (ps[1] * H.Fc[2] - ps[2] * H.Fc[1]), H.T0[1] - (ps[2] * H.Fc[0] - ps[0] * H.Fc[2]),
+                         H.T0[2] - (ps[0] * H.Fc[1] - ps[1] * H.Fc[0])};
+  // w' = I_w^-1 (tau - w x I_w w) = R I_b^-1 (R' tau - wb x I_b wb), wb = R' w: a cross product turns with its factors.  R' and R
+  // are applied as the three plane rotations they are made of (R' = Rx' Ry' Rz'): the nine entries of R are never formed.
+  const double wy0 = k1 * wz0 - s1 * w[2], wy2 = s1 * wz0 + k1 * w[2];           // Ry' (Rz' w)
+  const double wb[3] = {wy0, k0 * wz1 + s0 * wy2, -s0 * wz1 + k0 * wy2};         // Rx' ...
+  const double tz0 = k2 * tau[0] + s2 * tau[1], tz1 = -s2 * tau[0] + k2 * tau[1];
+  const double ty0 = k1 * tz0 - s1 * tau[2], ty2 = s1 * tz0 + k1 * tau[2];
+  const double tb[3] = {ty0, k0 * tz1 + s0 * ty2, -s0 * tz1 + k0 * ty2};
+  double Lb[3], ab[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Lb[i] = P.Ib[3 * i] * wb[0] + P.Ib[3 * i + 1] * wb[1] + P.Ib[3 * i + 2] * wb[2];
+  const double y[3] = {tb[0] - (wb[1] * Lb[2] - wb[2] * Lb[1]), tb[1] - (wb[2] * Lb[0] - wb[0] * Lb[2]), tb[2] - (wb[0] * Lb[1] - wb[1] * Lb[0])};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) ab[i] = P.Ibinv[3 * i] * y[0] + P.Ibinv[3 * i + 1] * y[1] + P.Ibinv[3 * i + 2] * y[2];
+  const double ax1 = k0 * ab[1] - s0 * ab[2], ax2 = s0 * ab[1] + k0 * ab[2];     // Rx ab
+  const double ay0 = k1 * ab[0] + s1 * ax2, ay2 = -s1 * ab[0] + k1 * ax2;        // Ry ...
+  dw[0] = k2 * ay0 - s2 * ax1; dw[1] = s2 * ay0 + k2 * ax1; dw[2] = ay2;         // Rz ...
+  return fabs(k1) >= 0x1p-22;
+}
+
+// One control period: xn = the state after S.substeps steps of S.hs from x.  c0, c1: the contact bits as 0.0 / 1.0.  The inputs
+// come as the fp32 values of the ABI and are widened where they are used: widened up front, 36 of them hold 72 registers at once.
+// Returns false, with xn all NaN, for a bad instance.
+// Both integrators are one loop over stages with ONE call of plant_rate: stage j starts from the step's state + c_j hs (rate of
+// stage j - 1), its rate enters the step with weight b_j; Euler is the one-stage scheme c = {0}, b = {1}, RK4
+// c = {0, 1/2, 1/2, 1}, b = {1, 2, 2, 1} / 6.  The acceleration a is constant over the period, so v's stage rates are a and p's
+// are v + c_{j-1} hs a: their weighted sums are written out (v += hs a;  p += hs v, + hs^2 / 2 a under RK4) instead of being
+// carried -- the same scheme, 24 values fewer in registers.
+__device__ __forceinline__ bool plant_step(const PlantParams& P, const PlantScheme& S, const float (&x)[12],
+                                           const float (&u)[12], const float (&r)[6], const double c0, const double c1,
+                                           const float (&w)[6], double (&xn)[12]) {
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) ok = ok && plant_finite(x[i]) && plant_finite(u[i]);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) ok = ok && plant_finite(r[i]) && plant_finite(w[i]);
+  const PlantHeld H = plant_held(P, u, r, c0, c1, w);
+  double e[3], p[3], om[3], v[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { e[i] = (double)x[i]; p[i] = (double)x[3 + i]; om[i] = (double)x[6 + i]; v[i] = (double)x[9 + i]; }
+  for (int s = 0; s < S.substeps; ++s) {
+    double ke[3] = {0.0, 0.0, 0.0}, kw[3] = {0.0, 0.0, 0.0}, ae[3] = {0.0, 0.0, 0.0}, aw[3] = {0.0, 0.0, 0.0};
+    double cprev = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < S.stages; ++j) {
+      const double cj = j == 0 ? 0.0 : (j == 3 ? S.hs : S.hh), bj = (j == 1 || j == 2) ? 2.0 : 1.0;
+      const double es[3] = {e[0] + cj * ke[0], e[1] + cj * ke[1], e[2] + cj * ke[2]};
+      ok = plant_rate(P, H, es, p, v, cprev, om, cj, kw, ke, kw) && ok;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { ae[i] += bj * ke[i]; aw[i] += bj * kw[i]; }
+      cprev = cj;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      e[i] += S.wsum * ae[i]; om[i] += S.wsum * aw[i];
+      p[i] += S.hs * v[i] + S.half2 * H.a[i];
+      v[i] += S.hs * H.a[i];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { xn[i] = e[i]; xn[3 + i] = p[i]; xn[6 + i] = om[i]; xn[9 + i] = v[i]; }
+  if (!ok) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) xn[i] = __builtin_nan("");
+  }
+  return ok;
+}
+
+// The landing rule of the closed loop: leg g (side +1 for leg 0, -1 for leg 1) lands when its row-0 contact bit is 0 at schedule
+// step k0 (this period) and 1 at k1 (the next); its foothold then becomes the swing controller's own target (REF:428-435) at
+// the state x, on the ground.  Returns whether the leg lands; r is rewritten only then.
+__device__ __forceinline__ bool plant_land(const PlantParams& P, const int k0, const int k1, const int offset, const int period,
+                                           const int duty, const double side, const double (&x)[12], const double cmd_x,
+                                           const double cmd_y, double (&r)[3]) {
+  const bool lands = !in_stance(k0, offset, period, duty) && in_stance(k1, offset, period, duty);
+  if (lands) {
+    r[0] = foothold_target(x[3], x[9], P.h, P.dt, P.kv, cmd_x);
+    r[1] = foothold_target(x[4], x[10], P.h, P.dt, P.kv, cmd_y) + 0.04 * side;
+    r[2] = 0.0;
+  }
+  return lands;
+}
+
+}  // namespace bmpc
+
+#ifndef BMPC_EMU
+#include "bmpc_lowlevel.hip"                   // GaitParams, py_floordiv: the schedule step of a time, as gait_kernel finds it
+
+namespace bmpc {
+
+// the gait rule as the landing needs it: bmpc_gait, and whether landing legs get a new foothold
+struct PlantGait { int period, offset[2], duty[2], move_feet; };
+
+// Both kernels ask for four waves per SIMD (the second launch bound): 128 registers, which the step fits without spilling; left
+// to itself the scheduler spreads the same code over a few more.
+// x_next[B][12] from x_fb[B][12], u0[B][12], foot[B][6], contact0[B][2] and wrench[B][6] (or null: none)
+__global__ void __launch_bounds__(256, 4)
+plant_step_kernel(const PlantParams P, const PlantScheme S, const int B, const float* __restrict__ x_fb, const float* __restrict__ u0,
+                  const float* __restrict__ foot, const uint8_t* __restrict__ contact0, const float* __restrict__ wrench,
+                  float* __restrict__ x_next) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float x[12], u[12], r[6], w[6];
+  double xn[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { x[i] = x_fb[(size_t)b * 12 + i]; u[i] = u0[(size_t)b * 12 + i]; }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { r[i] = foot[(size_t)b * 6 + i]; w[i] = wrench ? wrench[(size_t)b * 6 + i] : 0.f; }
+  const double c0 = contact0[(size_t)b * 2] ? 1.0 : 0.0, c1 = contact0[(size_t)b * 2 + 1] ? 1.0 : 0.0;
+  plant_step(P, S, x, u, r, c0, c1, w, xn);
+#pragma unroll
+  for (int i = 0; i < 12; ++i) x_next[(size_t)b * 12 + i] = (float)xn[i];
+}
+
+// One closed-loop period of bmpc_simulate_device, in place of rollout_feedback_kernel: the plant integrates x_fb under
+// controls[b, 0, :], foot[b], row 0 of this period's contact table and the push (null: not active in this period); t += dt;
+// with G.move_feet the legs that land at the new time get the foothold target at the NEW state; the applied control, the new
+// state, the footholds after the update and the iteration count are recorded, status_any |= status (| BMPC_NUMERICAL for a
+// bad plant step).  One thread per instance.
+__global__ void __launch_bounds__(256, 4)
+simulate_feedback_kernel(const PlantParams P, const PlantScheme S, const PlantGait G, const int B,
+                         const float* __restrict__ controls, const uint8_t* __restrict__ contact, const int32_t* __restrict__ iters,
+                         const int32_t* __restrict__ status, const float* __restrict__ push, const float* __restrict__ x_cmd,
+                         float* __restrict__ x_fb, float* foot, double* __restrict__ t, float* __restrict__ u0_out,
+                         float* __restrict__ x_out, float* __restrict__ foot_out, int32_t* __restrict__ iters_out,
+                         int32_t* __restrict__ status_any) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int h = (int)P.h;
+  const float* u0 = controls + (size_t)b * h * 12;
+  float x[12], u[12], r[6], w[6];
+  double xn[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { x[i] = x_fb[(size_t)b * 12 + i]; u[i] = u0[i]; }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { r[i] = foot[(size_t)b * 6 + i]; w[i] = push ? push[(size_t)b * 6 + i] : 0.f; }
+  // What does not depend on the step comes first (the applied control, the iteration count, the solver's status): behind the
+  // step, its loads are hoisted above the stages and sit in registers there.
+  if (u0_out) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) u0_out[(size_t)b * 12 + i] = u[i];
+  }
+  if (iters_out) iters_out[b] = iters[b];
+  if (status_any) status_any[b] |= status[b];
+  const uint8_t* row0 = contact + (size_t)b * h * 2;
+  const bool ok = plant_step(P, S, x, u, r, row0[0] ? 1.0 : 0.0, row0[1] ? 1.0 : 0.0, w, xn);
+  if (!ok && status_any) status_any[b] |= 2;      // BMPC_NUMERICAL
+  float xf[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    xf[i] = (float)xn[i];
+    x_fb[(size_t)b * 12 + i] = xf[i];
+    if (x_out) x_out[(size_t)b * 12 + i] = xf[i];
+  }
+  const double t0 = t[b], t1 = t0 + P.dt;
+  t[b] = t1;
+  // the schedule steps of t0 and t1, as gait_kernel finds them (REF:56-57)
+  double ka = fmod(py_floordiv(t0, P.dt), P.h), kb = fmod(py_floordiv(t1, P.dt), P.h);
+  if (ka < 0) ka += P.h;
+  if (kb < 0) kb += P.h;
+  const int k0 = (int)ka, k1 = (int)kb;
+  float rf[6];                                   // (`foot` is not __restrict__: read again here, not carried through the stages)
+#pragma unroll
+  for (int i = 0; i < 6; ++i) rf[i] = foot[(size_t)b * 6 + i];
+  if (G.move_feet) {
+    // the target is taken at the fp32 state the next solve will see
+    double xs[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) xs[i] = xf[i];
+    const double cx = x_cmd ? (double)x_cmd[(size_t)b * 12 + 3] : P.cmd_x, cy = x_cmd ? (double)x_cmd[(size_t)b * 12 + 4] : P.cmd_y;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      double rg[3];
+      if (plant_land(P, k0, k1, G.offset[g], G.period, G.duty[g], g == 0 ? 1.0 : -1.0, xs, cx, cy, rg)) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          rf[3 * g + i] = (float)rg[i];
+          foot[(size_t)b * 6 + 3 * g + i] = rf[3 * g + i];
+        }
+      }
+    }
+  }
+  if (foot_out) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) foot_out[(size_t)b * 6 + i] = rf[i];
+  }
+}
+
+}  // namespace bmpc
+#endif
+#endif

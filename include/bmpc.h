@@ -545,6 +545,63 @@ int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const floa
                         float* u0_traj, float* x_traj, int32_t* iters_traj, int32_t* status_any, void* stream);
 int bmpc_set_dispatch_order(bmpc_handle h, const int32_t* order_dev, int longest_first_rollouts);
 
+/*
+ * Closed-loop simulation (added under ABI 13; BMPC_ABI_VERSION is unchanged because the addition is purely additive, so a caller
+ * detects it by the symbol, e.g. dlsym(lib, "bmpc_simulate_device")).  bmpc_rollout_device closes the loop on the controller's own
+ * prediction with feet that never move; these entries close it on a PLANT: the nonlinear single rigid body, with feet that land
+ * where the swing controller steers them and an optional push.  What a rigid body makes of the controller, per instance.
+ *
+ * The plant.  State x = [e(3), p(3), w(3), v(3)], e = [roll, pitch, yaw], w and v in the world frame (REF:13).  Held over one control
+ * period dt: the controls u = [f1 f2 m1 m2], the feet r_0, r_1, the contact bits c_0, c_1 and an external wrench [F(3), M(3)] in
+ * the world frame.  With R = Rz(e2) Ry(e1) Rx(e0) (REF:124-138) and I_w = R I R':
+ *   e0' = (cos e2 wx + sin e2 wy) / cos e1,  e1' = -sin e2 wx + cos e2 wy,  e2' = wz + sin e1 e0',  p' = v,
+ *   w' = I_w^-1 (tau - w x I_w w),  tau = sum_g c_g [(r_g - p) x f_g + m_g] + M,   v' = (sum_g c_g f_g + F) / m + (0, 0, -g).
+ * A leg whose contact bit is 0 transmits nothing.  This is not the controller's model (REF:148-185; DESIGN.md lists the
+ * differences).  Integration: `substeps` in [1, 64] steps of dt / substeps, explicit Euler (BMPC_PLANT_EULER: every component from
+ * the old stage values, the form of REF:183-184) or classical Runge-Kutta (BMPC_PLANT_RK4).  fp64 arithmetic on the fp32 arrays.
+ * A non-finite input of an instance, or |cos e1| < 2^-22 at any stage, makes the whole next state of that instance NaN; no other
+ * instance is touched.
+ *   bmpc_plant_default(p)      RK4, 4 substeps, move_feet 1, no push
+ *   bmpc_plant_step_device     one period: x_fb [B][12], u0 [B][12], foot [B][6], contact0 [B][2], wrench [B][6] or NULL
+ *                              -> x_next [B][12].  DEVICE pointers, asynchronous on `stream`; move_feet / push_* are not used
+ *   bmpc_plant_step            the same with HOST pointers, synchronous (staged through the handle's own stream)
+ *
+ * bmpc_simulate_device: bmpc_rollout_device's loop (schedule, optional longest-first order, solve; warm start and
+ * bmpc_set_dispatch_order honoured alike; one stream, no host arithmetic, no synchronisation) with another feedback step.  Per
+ * period s:  x_fb <- plant(x_fb, controls[:, 0], foot, row 0 of the period's contact table, push if push_from <= s < push_from +
+ * push_steps);  t += dt;  with move_feet != 0, a leg whose row-0 contact bit is 0 at the old t and 1 at the new one (the gait rule of
+ * bmpc_contact_sequence) LANDS: its foothold becomes the swing controller's target (REF:428-435) at the new state as stored (fp32),
+ *   x = p_x + v_x (h / 2 dt) / 2 + kv (p_x - cmd_x),  y likewise + 0.04 side (side +1 for leg 0, -1 for leg 1),  z = 0,
+ * with cmd the per-instance x_cmd where given, else the handle's; every other foothold stays.
+ *   x_fb [B][12] in/out, foot [B][6] in/out, t [B] fp64 in/out; gait, x_cmd, mu as for bmpc_rollout_device; push [B][6] or NULL;
+ *   u0_traj [steps][B][12], x_traj [steps][B][12] (state after each period), foot_traj [steps][B][6] (footholds after each period's
+ *   update), iters_traj [steps][B], status_any [B] (OR of the per-period status values, and BMPC_NUMERICAL where a plant step went
+ *   bad): each may be NULL.
+ * `plant` NULL is the default.  substeps outside [1, 64], an unknown integrator, a negative push_from or push_steps (checked
+ * first, before the handle), a NULL handle, or a NULL required pointer is BMPC_ERR_INVALID, before any device call; B == 0 (and
+ * steps == 0) succeeds.
+ */
+enum bmpc_plant_integrator {
+  BMPC_PLANT_EULER = 0,
+  BMPC_PLANT_RK4 = 1
+};
+typedef struct bmpc_plant {
+  int32_t integrator;        /* BMPC_PLANT_EULER / BMPC_PLANT_RK4 */
+  int32_t substeps;          /* 1 .. 64 */
+  int32_t move_feet;         /* bmpc_simulate_device: landing legs get a new foothold */
+  int32_t push_from;         /* bmpc_simulate_device: first period of the push */
+  int32_t push_steps;        /* ... and its number of periods (0: none) */
+} bmpc_plant;
+int bmpc_plant_default(bmpc_plant* p);
+int bmpc_plant_step(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
+                    const uint8_t* contact0, const float* wrench, float* x_next);
+int bmpc_plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
+                           const uint8_t* contact0, const float* wrench, float* x_next, void* stream);
+int bmpc_simulate_device(bmpc_handle h, int B, int steps, const bmpc_plant* plant, float* x_fb, float* foot, double* t,
+                         const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push,
+                         float* u0_traj, float* x_traj, float* foot_traj,
+                         int32_t* iters_traj, int32_t* status_any, void* stream);
+
 /* Diagnostics: when device_buf (DEVICE pointer, [max_batch][16] int64) is non-NULL every later solve
  * writes per-instance shader-clock stamps {setup, block algebra, dense sweeps, total, iters,
  * factorisations, -, -, iteration phases P0..P5, stop test + adaptation, -}; NULL switches it off
