@@ -26,19 +26,37 @@ def r32(a):
     return None if a is None else np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
 
 
-def yardstick(g, i):
-    """dict(cost, objective, violation (4,), states (h,13)) of instance i of group g, fp64."""
+def oracle_objects(g, i, mods=None):
+    """(orc.MPC, orc.Biped, dt) of instance i of group g.  `mods` (default: the group's own "mods" entry, else none) is a pair
+    (change of the MPC object or None, of the Biped object or None) as in util.PARAM_CASES, applied to the MPC and to a copy of the
+    group's Biped; dt is then the MPC's, else the module constant."""
+    import copy
+    from oracle import bmpc_oracle as orc
+    mpc = orc.MPC()
+    mpc.h, mpc.x_cmd = g["h"], r32(g["x_cmd"][i])
+    mods = g.get("mods") if mods is None else mods
+    if mods is None:
+        return mpc, g["biped"], DT
+    biped = copy.deepcopy(g["biped"])
+    for mod, obj in zip(mods, (mpc, biped)):
+        if mod:
+            mod(obj)
+    assert mpc.h == g["h"], "a case of an evaluation group must keep the horizon"
+    return mpc, biped, float(mpc.dt)
+
+
+def yardstick(g, i, mods=None):
+    """dict(cost, objective, violation (4,), states (h,13)) of instance i of group g, fp64; `mods`: see oracle_objects."""
     from oracle import bmpc_oracle as orc
     h = g["h"]
-    mpc = orc.MPC()
-    mpc.h, mpc.x_cmd = h, r32(g["x_cmd"][i])
+    mpc, biped, dt = oracle_objects(g, i, mods)
     xr = None if g["x_ref"] is None else np.vstack([r32(g["x_ref"][i][:12]), np.ones((1, h))])
     fr = None if g["foot_ref"] is None else r32(g["foot_ref"][i])
     mu = None if g["mu"] is None else r32(g["mu"][i])
     U = r32(g["controls"][i]).reshape(-1)
-    t = (int(g["phase"][i]) + 0.5) * DT
+    t = (int(g["phase"][i]) + 0.5) * dt
     with rc.supplied(orc, xr, fr):
-        sp = orc.build_sparse_qp(r32(g["x_fb"][i]), t, r32(g["foot"][i]), mpc, g["biped"], np.asarray(g["contact"][i]),
+        sp = orc.build_sparse_qp(r32(g["x_fb"][i]), t, r32(g["foot"][i]), mpc, biped, np.asarray(g["contact"][i]),
                                  half=g["half"], mu_steps=mu)
     assert orc.phase_index(t, mpc) == int(g["phase"][i])
     A, b = sp["A"], sp["b"]
@@ -53,9 +71,9 @@ def yardstick(g, i):
     return dict(cost=cost, objective=objective, violation=viol, states=X.reshape(h, 13))
 
 
-def yardstick_group(g, idx=None):
+def yardstick_group(g, idx=None, mods=None):
     idx = range(g["x_fb"].shape[0]) if idx is None else idx
-    ys = [yardstick(g, int(i)) for i in idx]
+    ys = [yardstick(g, int(i), mods) for i in idx]
     return {k: np.stack([np.asarray(y[k]) for y in ys]) for k in ("cost", "objective", "violation", "states")}
 
 
@@ -70,14 +88,16 @@ def metrics(got, ref):
                 violation=vi)
 
 
-def check(got, ref, where):
-    """Prints the maxima of the four metrics, then asserts the acceptance bound (util.REL_TOL) and the regression bound of each."""
+def check(got, ref, where, reg_bound=None):
+    """Prints the maxima of the four metrics, then asserts the acceptance bound (util.REL_TOL) and the regression bound of each
+    (REG_BOUND, or `reg_bound` for case sets that hold their own)."""
+    reg_bound = REG_BOUND if reg_bound is None else reg_bound
     m = {k: float(v.max()) for k, v in metrics(got, ref).items()}
     print("evaluate metrics", where, " ".join(f"{k}={v:.3e}" for k, v in m.items()))
     assert all(np.isfinite(got[k]).all() for k in ("cost", "objective", "violation", "states")), where
     for k, v in m.items():
         assert v <= util.REL_TOL, (where, k, v)
-        assert v <= REG_BOUND[k], (where, k, v)
+        assert v <= reg_bound[k], (where, k, v)
     return m
 
 
@@ -192,13 +212,19 @@ def kernel_args(g, idx=None):
                 x_cmd=g["x_cmd"][sl], mu=None if g["mu"] is None else g["mu"][sl], x_ref=xr, foot_ref=fr)
 
 
-def cparams_of(g, path=0):
+def cparams_of(g, path=0, mods=None):
+    """The parameter block of group g on kernel family `path`: the horizon, the half period and the four bound vectors of the group's
+    Biped; `mods` (default: the group's own "mods" entry, else none; see oracle_objects) is then applied to the package's objects."""
     import biped_mpc_py_amd as bm
     mpc = bm.MPC()
     mpc.h = g["h"]
     b = bm.Biped()
     for k in ("f_max", "f_min", "tau_max", "tau_min"):
         setattr(b, k, np.asarray(getattr(g["biped"], k), float).reshape(-1))
+    mods = g.get("mods") if mods is None else mods
+    for mod, obj in zip(mods or (), (mpc, b)):
+        if mod:
+            mod(obj)
     return bm.pack_params(mpc, b, half=g["half"], solver_options=dict(path=path) if path else None)
 
 

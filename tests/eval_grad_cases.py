@@ -45,17 +45,16 @@ OPT_SOLVER_MARGIN = util.REL_TOL
 OPT_TOL_SOLVER = {h: v + OPT_SOLVER_MARGIN for h, v in OPT_TOL.items()}
 
 
-def yardstick(g, i):
-    """dict(cost, grad_u (h,12), grad_x0 (12,)) of instance i of group g, fp64."""
+def yardstick(g, i, mods=None):
+    """dict(cost, grad_u (h,12), grad_x0 (12,)) of instance i of group g, fp64; `mods`: see eval_cases.oracle_objects."""
     from oracle import bmpc_oracle as orc
     h = g["h"]
-    mpc = orc.MPC()
-    mpc.h, mpc.x_cmd = h, ec.r32(g["x_cmd"][i])
+    mpc, biped, dt = ec.oracle_objects(g, i, mods)
     mu = None if g["mu"] is None else ec.r32(g["mu"][i])
     U = ec.r32(g["controls"][i]).reshape(-1)
-    t = (int(g["phase"][i]) + 0.5) * ec.DT
+    t = (int(g["phase"][i]) + 0.5) * dt
     x_fb, foot, contact = ec.r32(g["x_fb"][i]), ec.r32(g["foot"][i]), np.asarray(g["contact"][i])
-    build = lambda x: orc.build_sparse_qp(x, t, foot, mpc, g["biped"], contact, half=g["half"], mu_steps=mu)
+    build = lambda x: orc.build_sparse_qp(x, t, foot, mpc, biped, contact, half=g["half"], mu_steps=mu)
     xr = None if g["x_ref"] is None else np.vstack([ec.r32(g["x_ref"][i][:12]), np.ones((1, h))])
     fr = None if g["foot_ref"] is None else ec.r32(g["foot_ref"][i])
     if xr is None or fr is None:                 # generated: the oracle's own, pinned from here on
@@ -79,9 +78,9 @@ def yardstick(g, i):
     return dict(cost=cost, grad_u=grad_u.reshape(h, 12), grad_x0=grad_x0)
 
 
-def yardstick_group(g, idx=None):
+def yardstick_group(g, idx=None, mods=None):
     idx = range(g["x_fb"].shape[0]) if idx is None else idx
-    ys = [yardstick(g, int(i)) for i in idx]
+    ys = [yardstick(g, int(i), mods) for i in idx]
     return {k: np.stack([np.asarray(y[k]) for y in ys]) for k in KEYS}
 
 
@@ -95,15 +94,17 @@ def metrics(got, ref):
     return out
 
 
-def check(got, ref, where):
-    """Prints the maxima of the three metrics, then asserts the acceptance bound (util.REL_TOL) and the regression bound of each."""
+def check(got, ref, where, reg_bound=None):
+    """Prints the maxima of the three metrics, then asserts the acceptance bound (util.REL_TOL) and the regression bound of each
+    (REG_BOUND, or `reg_bound` for case sets that hold their own)."""
+    reg_bound = REG_BOUND if reg_bound is None else reg_bound
     m = {k: float(v.max()) for k, v in metrics(got, ref).items()}
     print("evaluate_grad metrics", where, " ".join(f"{k}={v:.3e}" for k, v in m.items()),
           "|grad_u| %.3g |grad_x0| %.3g" % (np.abs(ref["grad_u"]).max(), np.abs(ref["grad_x0"]).max()))
     assert all(np.isfinite(got[k]).all() for k in KEYS), where
     for k, v in m.items():
         assert v <= util.REL_TOL, (where, k, v)
-        assert v <= REG_BOUND[k], (where, k, v)
+        assert v <= reg_bound[k], (where, k, v)
     return m
 
 

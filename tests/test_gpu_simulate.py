@@ -74,25 +74,32 @@ def _times(t0, dt):
     return ts
 
 
-def _check_periods(s, x0, foot0, t0, r, push=None, window=(0, 0), expect_wrench=True):
-    """(a) - (d) of the module docstring for every period; returns the number of landings seen per leg."""
+def _check_periods(s, x0, foot0, t0, r, push=None, window=(0, 0), expect_wrench=True, plant_kw=None, x_cmd=None, gait=None,
+                   integrator="rk4", substeps=4):
+    """(a) - (d) of the module docstring for every period; returns the number of landings seen per leg.  `plant_kw`: the model's
+    I_b, m, g where the handle's are not the defaults; `x_cmd` (B,12): the per-instance commands the simulation ran with; `gait`
+    (period, offset, duty), `integrator`, `substeps`: what it ran with where that was not the default."""
     import torch
     h, dt = s.h, float(s.cparams.dt)
     half = int(s.cparams.half)
-    gait = (2 * half, (0, half), (half, half))
+    gait_kw = {} if gait is None else dict(period=gait[0], offset=gait[1], duty=gait[2])
+    gait = (2 * half, (0, half), (half, half)) if gait is None else gait
+    plant_kw = {k: v for k, v in (plant_kw or {}).items() if k != "dt"}
+    cmd_dev = None if x_cmd is None else _cuda(x_cmd, np.float32)
     ts = _times(t0, dt)
     landed = np.zeros(2, int)
     B = x0.shape[0]
     for k in range(K):
         xs = x0 if k == 0 else r["x"][k - 1]
         fs = foot0 if k == 0 else r["foot"][k - 1]
-        phase, contact = s.contact_sequence_device(_cuda(ts[k], np.float64))
+        phase, contact = s.contact_sequence_device(_cuda(ts[k], np.float64), **gait_kw)
         s.reset_warm_start()
-        u, _ = s.solve_device(_cuda(xs, np.float32), _cuda(fs, np.float32), contact, phase)
+        u, _ = s.solve_device(_cuda(xs, np.float32), _cuda(fs, np.float32), contact, phase, x_cmd=cmd_dev)
         assert torch.equal(u[:, 0, :].cpu(), torch.from_numpy(r["u0"][k])), ("u0", k)                          # (a)
         c0 = contact[:, 0, :].cpu().numpy()
         active = push is not None and window[0] <= k < window[0] + window[1]
-        ref = pm.step_batch(xs, r["u0"][k], fs, c0, push if (active and expect_wrench) else None, integrator="rk4", substeps=4, dt=dt)
+        ref = pm.step_batch(xs, r["u0"][k], fs, c0, push if (active and expect_wrench) else None, integrator=integrator,
+                            substeps=substeps, dt=dt, **plant_kw)
         d = pm.ulp_diff(r["x"][k], ref)
         if active and not expect_wrench:
             pushed = np.abs(push).max(1) > 0
@@ -102,8 +109,9 @@ def _check_periods(s, x0, foot0, t0, r, push=None, window=(0, 0), expect_wrench=
         k0 = s.contact_sequence_device(_cuda(ts[k], np.float64))[0].cpu().numpy()
         k1 = s.contact_sequence_device(_cuda(ts[k + 1], np.float64))[0].cpu().numpy()
         for b in range(B):
+            cmd = (float(s.cparams.x_cmd[3]), float(s.cparams.x_cmd[4])) if x_cmd is None else x_cmd[b, 3:5].astype(np.float64)
             fr, lands = pm.landing(r["x"][k][b].astype(np.float64), fs[b], int(k0[b]), int(k1[b]), gait[0], gait[1], gait[2], h=h, dt=dt,
-                                   kv=float(s.cparams.kv))
+                                   kv=float(s.cparams.kv), cmd=cmd)
             assert pm.ulp_diff(r["foot"][k][b], fr, atol=0.0).max() <= 1.0, ("foot", k, b)                         # (c)
             for g in range(2):
                 if not lands[g]:
@@ -124,6 +132,33 @@ def test_simulate_is_the_composition_of_verified_parts(h, path):
     landed = _check_periods(s, x0, foot0, t0, r)
     assert (landed >= B // 2).all(), landed             # both legs land
     assert (r["status_any"] == 0).all() and np.isfinite(r["x"]).all()
+
+
+@pytest.mark.parametrize("run", ["combined_h7_stage", "euler_h10_dense"])
+def test_simulate_at_a_parameter_case_with_per_instance_commands(run):
+    """The closed loop away from the defaults (tests/param_cases.py CLOSED_LOOP_RUNS), checked period by period like the default one:
+    the combined case (m, a non-diagonal I_b, g, dt) on the h = 7 stage family under a custom gait, and explicit Euler with three
+    substeps at I_nondiagonal on the h = 10 dense family -- both with per-instance commands whose x, y entries are not zero, the branch
+    of the landing rule that reads them.  B = 33, 12 periods; every instance lands each leg at least once."""
+    import biped_mpc_py_amd as bm
+    from tests import param_cases as pc
+    assert K == pc.CLOSED_LOOP_K
+    c = pc.CLOSED_LOOP_RUNS[run]
+    mpc, biped = pc.objects(bm, c["case"], h=c["h"])
+    s = bm.BatchSolver(mpc=mpc, biped=biped, solver_options=dict(path=c["path"]), max_batch=64)
+    assert s._lib.bmpc_solver_path(s._h) == c["path"]
+    x0, foot0, t0, x_cmd = pc.closed_loop_start(run)
+    period, offset, duty = c["gait"]
+    r = _simulate(s, x0, foot0, t0, x_cmd=_cuda(x_cmd, np.float32), period=period, offset=offset, duty=duty,
+                  integrator=c["integrator"], substeps=c["substeps"])
+    landed = _check_periods(s, x0, foot0, t0, r, plant_kw=pc.plant_kw(c["case"]), x_cmd=x_cmd, gait=c["gait"],
+                            integrator=c["integrator"], substeps=c["substeps"])
+    print(run, "landings per leg", landed, "iterations mean %.1f max %d" % (r["iters"].mean(), r["iters"].max()))
+    assert (landed >= x0.shape[0]).all(), landed            # (every instance lands each leg: test_the_closed_loop_runs_let_both_legs_land)
+    assert (r["status_any"] == 0).all() and np.isfinite(r["x"]).all()
+    # the commands were read: the footholds of the same run without them differ
+    plain = _simulate(s, x0, foot0, t0, period=period, offset=offset, duty=duty, integrator=c["integrator"], substeps=c["substeps"])
+    assert not np.array_equal(plain["foot_end"], r["foot_end"])
 
 
 def test_move_feet_off_leaves_the_footholds():
