@@ -27,6 +27,7 @@ EXPORTS = (
     "bmpc_gait_default", "bmpc_contact_sequence", "bmpc_contact_sequence_device",
     "bmpc_set_warm_start", "bmpc_reset_warm_start", "bmpc_rollout_device", "bmpc_set_dispatch_order",
     "bmpc_plant_default", "bmpc_plant_step", "bmpc_plant_step_device", "bmpc_simulate_device",
+    "bmpc_plant_step_body", "bmpc_plant_step_body_device", "bmpc_simulate_body_device",
 )
 
 
@@ -41,6 +42,17 @@ class CPlant(C.Structure):
 
 
 PLANT_INTEGRATORS = {"euler": 0, "rk4": 1}     # enum bmpc_plant_integrator
+
+
+class CPlantBody(C.Structure):
+    """`bmpc_plant_body` of include/bmpc.h: the plant's m [B], I [B][9], g [B] per instance (NULL: the handle's value)."""
+    _fields_ = [(n, C.c_void_p) for n in ("m", "I", "g")]
+
+
+class CSimOutcome(C.Structure):
+    """`bmpc_sim_outcome` of include/bmpc.h: the fall thresholds and the per-instance outcome arrays (NULL: not wanted)."""
+    _fields_ = [("tilt_max", C.c_double), ("z_min", C.c_double), ("first_fall", C.c_void_p), ("max_tilt", C.c_void_p),
+                ("min_z", C.c_void_p)]
 
 
 class CHostViews(C.Structure):
@@ -180,6 +192,10 @@ def load():
     lib.bmpc_plant_step.argtypes = [vp, ip, C.POINTER(CPlant)] + [vp] * 6
     lib.bmpc_plant_step_device.argtypes = [vp, ip, C.POINTER(CPlant)] + [vp] * 7
     lib.bmpc_simulate_device.argtypes = [vp, ip, ip, C.POINTER(CPlant), vp, vp, vp, C.POINTER(CGait)] + [vp] * 9
+    lib.bmpc_plant_step_body.argtypes = [vp, ip, C.POINTER(CPlant), C.POINTER(CPlantBody)] + [vp] * 6
+    lib.bmpc_plant_step_body_device.argtypes = [vp, ip, C.POINTER(CPlant), C.POINTER(CPlantBody)] + [vp] * 7
+    lib.bmpc_simulate_body_device.argtypes = [vp, ip, ip, C.POINTER(CPlant), C.POINTER(CPlantBody), vp, vp, vp, C.POINTER(CGait)] + \
+        [vp] * 8 + [C.POINTER(CSimOutcome), vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name != "bmpc_last_error":

@@ -702,11 +702,45 @@ class BatchSolver:
             raise ValueError("push_from and push_steps must be >= 0")
         return _lib.CPlant(_lib.PLANT_INTEGRATORS[integrator], int(substeps), 1 if move_feet else 0, int(push_from), int(push_steps))
 
-    def plant_step(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4):
+    @staticmethod
+    def _body_items(body):
+        """The members of a `body` mapping as (name, value, accepted shapes per B); an unknown key is a ValueError."""
+        if not hasattr(body, "keys") or set(body.keys()) - {"m", "I", "g"}:
+            raise ValueError("body must be a mapping with any of the keys 'm', 'I', 'g'")
+        return [(k, body.get(k), ((3, 3), (9,)) if k == "I" else ((),)) for k in ("m", "I", "g") if body.get(k) is not None]
+
+    @classmethod
+    def _body_host(cls, body, B):
+        """(`bmpc_plant_body` of host arrays, the arrays it points into) from a `body` mapping of float64 arrays."""
+        cb, keep = _lib.CPlantBody(), []
+        for k, v, shapes in cls._body_items(body):
+            v = np.asarray(v)
+            if v.dtype != np.float64 or v.shape[1:] not in shapes or v.shape[:1] != (B,):
+                raise ValueError(f"body[{k!r}] must be float64 of shape {' or '.join(str((B,) + s) for s in shapes)}, not {v.dtype} {v.shape}")
+            keep.append(np.ascontiguousarray(v))
+            setattr(cb, k, keep[-1].ctypes.data)
+        return cb, keep
+
+    @classmethod
+    def _body_device(cls, body, B, dev):
+        """`bmpc_plant_body` of device pointers from a `body` mapping of contiguous float64 tensors on `dev`."""
+        import torch
+        cb = _lib.CPlantBody()
+        for k, v, shapes in cls._body_items(body):
+            if not isinstance(v, torch.Tensor) or v.dtype != torch.float64 or v.device != dev or not v.is_contiguous() \
+                    or tuple(v.shape[1:]) not in shapes or tuple(v.shape[:1]) != (B,):
+                raise ValueError(f"body[{k!r}] must be a contiguous float64 tensor on {dev} of shape "
+                                 f"{' or '.join(str((B,) + s) for s in shapes)}")
+            setattr(cb, k, v.data_ptr())
+        return cb
+
+    def plant_step(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4, body=None):
         """One control period of the plant -- the nonlinear single rigid body of include/bmpc.h, NOT the controller's linear model --
         under held controls (`bmpc_plant_step`): x_fb (B,12), u0 (B,12) = [f1 f2 m1 m2], foot (B,6), contact0 (B,2) (a leg with bit 0
         transmits nothing), wrench (B,6) = [F, M] in the world frame or None -> x_next (B,12) fp64.  A bad instance (non-finite input,
-        pitch at +-90 degrees) comes back all NaN."""
+        pitch at +-90 degrees) comes back all NaN.  `body`: a mapping with any of m (B,), I (B,3,3) or (B,9), g (B,) as float64
+        arrays -- the PLANT's mass, body inertia and gravity per instance in place of this solver's (`bmpc_plant_step_body`); a bad
+        body (non-finite, m <= 0, singular I) comes back all NaN too."""
         plant = self._plant(integrator, substeps)
         a = np.asarray(x_fb, np.float32)
         if a.ndim != 2 or a.shape[1] != 12:
@@ -723,13 +757,20 @@ class BatchSolver:
                 raise ValueError(f"{name} must have shape {shp}, not {v.shape}")
             arrs.append(np.ascontiguousarray((v != 0).astype(np.uint8) if dt is None else v.astype(dt)))
         out = np.empty((B, 12), np.float32)
-        _lib.check(self._lib.bmpc_plant_step(self._h, B, C.byref(plant), *[_ptr(v) for v in arrs], _ptr(out)))
+        if body is None:
+            _lib.check(self._lib.bmpc_plant_step(self._h, B, C.byref(plant), *[_ptr(v) for v in arrs], _ptr(out)))
+        else:
+            cb, keep = self._body_host(body, B)
+            _lib.check(self._lib.bmpc_plant_step_body(self._h, B, C.byref(plant), C.byref(cb), *[_ptr(v) for v in arrs], _ptr(out)))
+            del keep
         return out.astype(np.float64)
 
-    def plant_step_device(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4, x_next=None, stream=None):
+    def plant_step_device(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4, x_next=None, stream=None,
+                          body=None):
         """`plant_step` on device tensors (`bmpc_plant_step_device`): float32 x_fb (B,12), u0 (B,12), foot (B,6), uint8 contact0 (B,2),
-        float32 wrench (B,6) or None -> x_next (B,12) float32 (allocated unless given).  Asynchronous on `stream` (default: torch's
-        current stream); nothing crosses PCIe."""
+        float32 wrench (B,6) or None -> x_next (B,12) float32 (allocated unless given).  `body`: as for `plant_step`, of float64
+        tensors on the device (`bmpc_plant_step_body_device`).  Asynchronous on `stream` (default: torch's current stream); nothing
+        crosses PCIe."""
         import torch
         plant = self._plant(integrator, substeps)
         dev = x_fb.device
@@ -738,31 +779,49 @@ class BatchSolver:
         if x_fb.dim() != 2:
             raise ValueError("x_fb must have shape (B, 12)")
         B = x_fb.shape[0]
+        cb = None if body is None else self._body_device(body, B, dev)
         if x_next is None:
             x_next = torch.empty((B, 12), dtype=torch.float32, device=dev)
         args = [_tensor_ptr(x_fb, torch.float32, (B, 12), dev), _tensor_ptr(u0, torch.float32, (B, 12), dev),
                 _tensor_ptr(foot, torch.float32, (B, 6), dev), _tensor_ptr(contact0, torch.uint8, (B, 2), dev),
                 _tensor_ptr(wrench, torch.float32, (B, 6), dev), _tensor_ptr(x_next, torch.float32, (B, 12), dev)]
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        _lib.check(self._lib.bmpc_plant_step_device(self._h, B, C.byref(plant), *args, st))
+        if cb is None:
+            _lib.check(self._lib.bmpc_plant_step_device(self._h, B, C.byref(plant), *args, st))
+        else:
+            _lib.check(self._lib.bmpc_plant_step_body_device(self._h, B, C.byref(plant), C.byref(cb), *args, st))
         return x_next
 
     def simulate_device(self, x_fb, foot, t, steps, x_cmd=None, mu=None, period=None, offset=None, duty=None, integrator="rk4",
-                        substeps=4, move_feet=True, push=None, push_from=0, push_steps=0, want_iters=True, stream=None):
+                        substeps=4, move_feet=True, push=None, push_from=0, push_steps=0, want_iters=True, stream=None, body=None,
+                        fall=None):
         """`steps` closed-loop control periods against the plant of `plant_step` (`bmpc_simulate_device`): `rollout_device`'s loop
         with the rigid body in place of the controller's own prediction.  x_fb (B,12) float32, foot (B,6) float32 and t (B,) float64
         are advanced IN PLACE (so `foot` must be writable): with `move_feet` a leg that lands gets the swing controller's foothold
         target at the new state.  push (B,6) float32 = [F, M] (world frame) or None acts in periods push_from <= s < push_from +
         push_steps.  Returns dict(u0 (steps,B,12), x (steps,B,12), foot (steps,B,6) -- the footholds after each period's update --,
-        iters (steps,B) | None, status_any (B,)).  Asynchronous on `stream` (default: torch's current stream)."""
+        iters (steps,B) | None, status_any (B,)).  Asynchronous on `stream` (default: torch's current stream).
+        `body`: the PLANT's m (B,), I (B,3,3) or (B,9), g (B,) per instance as float64 device tensors (any subset; the rest is this
+        solver's) -- the controller inside the loop keeps this solver's model: one model, many bodies (`bmpc_simulate_body_device`).
+        `fall` = (tilt_max, z_min): the dict also carries first_fall (B,) int32 -- the first period after which
+        !(|roll| <= tilt_max and |pitch| <= tilt_max and p_z >= z_min), a NaN state included, or -1 --, max_tilt (B,) and min_z (B,)
+        float32, the extrema of max(|roll|, |pitch|) and p_z over the periods that are not NaN.  Fallen instances run on."""
         import torch
         plant = self._plant(integrator, substeps, move_feet, push_from, push_steps)
+        if fall is not None:
+            try:
+                tilt_max, z_min = (float(v) for v in fall)
+            except (TypeError, ValueError):
+                raise ValueError("fall must be a (tilt_max, z_min) pair") from None
+            if tilt_max != tilt_max or z_min != z_min:
+                raise ValueError("fall thresholds must not be NaN")
         dev = x_fb.device
         if dev.type != "cuda" or dev.index != self.device:
             raise ValueError(f"tensors must live on cuda:{self.device}")
         if x_fb.dim() != 2 or int(steps) < 0:
             raise ValueError("x_fb must have shape (B, 12) and steps must be >= 0")
         B, steps = x_fb.shape[0], int(steps)
+        cb = None if body is None else self._body_device(body, B, dev)
         args = [_tensor_ptr(x_fb, torch.float32, (B, 12), dev), _tensor_ptr(foot, torch.float32, (B, 6), dev),
                 _tensor_ptr(t, torch.float64, (B,), dev)]
         opt = [_tensor_ptr(x_cmd, torch.float32, (B, 12), dev), _tensor_ptr(mu, torch.float32, (B, self.h, 2), dev),
@@ -774,10 +833,23 @@ class BatchSolver:
         its = torch.empty((steps, B), dtype=torch.int32, device=dev) if want_iters else None
         st_any = torch.zeros(B, dtype=torch.int32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        _lib.check(self._lib.bmpc_simulate_device(
-            self._h, B, steps, C.byref(plant), *args, None if gait is None else C.byref(gait), *opt,
-            u0.data_ptr(), xt.data_ptr(), ft.data_ptr(), None if its is None else its.data_ptr(), st_any.data_ptr(), st))
-        return dict(u0=u0, x=xt, foot=ft, iters=its, status_any=st_any)
+        out = dict(u0=u0, x=xt, foot=ft, iters=its, status_any=st_any)
+        traj = [u0.data_ptr(), xt.data_ptr(), ft.data_ptr(), None if its is None else its.data_ptr(), st_any.data_ptr()]
+        if cb is None and fall is None:
+            _lib.check(self._lib.bmpc_simulate_device(
+                self._h, B, steps, C.byref(plant), *args, None if gait is None else C.byref(gait), *opt, *traj, st))
+            return out
+        co = None
+        if fall is not None:
+            # (filled here as the entry does it, so that steps == 0 or B == 0, where the entry touches nothing, reads the same)
+            out.update(first_fall=torch.full((B,), -1, dtype=torch.int32, device=dev),
+                       max_tilt=torch.full((B,), float("nan"), dtype=torch.float32, device=dev),
+                       min_z=torch.full((B,), float("nan"), dtype=torch.float32, device=dev))
+            co = _lib.CSimOutcome(tilt_max, z_min, out["first_fall"].data_ptr(), out["max_tilt"].data_ptr(), out["min_z"].data_ptr())
+        _lib.check(self._lib.bmpc_simulate_body_device(
+            self._h, B, steps, C.byref(plant), None if cb is None else C.byref(cb), *args, None if gait is None else C.byref(gait), *opt,
+            *traj, None if co is None else C.byref(co), st))
+        return out
 
     def last_kernel_ms(self):
         ms = C.c_float(-1.0)

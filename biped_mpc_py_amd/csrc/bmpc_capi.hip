@@ -232,6 +232,7 @@ struct bmpc_handle_s {
   DevBuf<float> ll_q, ll_qd, ll_pf, ll_u0, ll_tau;
   DevBuf<double> ll_t;
   DevBuf<uint8_t> ll_c0;
+  DevBuf<double> body_m, body_I, body_g;   // bmpc_plant_step_body: the host body on the device
   long long* prof_dev = nullptr;   // optional cycle-stamp buffer (bmpc_debug_set_profile)
   // receding-horizon warm start (bmpc_set_warm_start): solver state of the last batch, kept on the device
   DevBuf<double> warm;
@@ -1179,23 +1180,35 @@ static bmpc::PlantParams plant_params(bmpc_handle h) {
   return q;
 }
 
-int bmpc_plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
-                           const uint8_t* contact0, const float* wrench, float* x_next, void* stream) {
+// whether a body / an outcome asks for anything: without, the entries run the kernels of the handle's own body
+static bool has_body(const bmpc_plant_body* b) { return b && (b->m || b->I || b->g); }
+static bool has_outcome(const bmpc_sim_outcome* o) { return o && (o->first_fall || o->max_tilt || o->min_z); }
+
+// bmpc_plant_step_device and bmpc_plant_step_body_device: `body` null or empty launches plant_step_kernel
+static int plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const float* x_fb,
+                             const float* u0, const float* foot, const uint8_t* contact0, const float* wrench, float* x_next,
+                             void* stream) {
   bmpc_plant o;
   if (int rc = plant_opts(plant, &o); rc != BMPC_OK) return rc;
   if (int rc = check_batch(h, B); rc <= 0) return rc;
   if (!x_fb || !u0 || !foot || !contact0 || !x_next) return fail(BMPC_ERR_INVALID, "x_fb, u0, foot, contact0 and x_next must be non-null");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = pick_stream(h, stream);
-  hipLaunchKernelGGL(bmpc::plant_step_kernel, dim3((B + 255) / 256), dim3(256), 0, st, plant_params(h),
-                     bmpc::plant_scheme(h->params.dt, o.integrator, o.substeps), B, x_fb, u0, foot, contact0, wrench, x_next);
+  const bmpc::PlantScheme S = bmpc::plant_scheme(h->params.dt, o.integrator, o.substeps);
+  if (has_body(body))
+    hipLaunchKernelGGL(bmpc::plant_step_body_kernel, dim3((B + 255) / 256), dim3(256), 0, st, plant_params(h),
+                       bmpc::PlantBody{body->m, body->I, body->g}, S, B, x_fb, u0, foot, contact0, wrench, x_next);
+  else
+    hipLaunchKernelGGL(bmpc::plant_step_kernel, dim3((B + 255) / 256), dim3(256), 0, st, plant_params(h), S, B, x_fb, u0, foot,
+                       contact0, wrench, x_next);
   HIP_TRY(hipGetLastError());
   return BMPC_OK;
 }
 
+// bmpc_plant_step and bmpc_plant_step_body
 // (staging: the buffers of the low-level host entries -- ll_pf holds foot positions there too; ll_q the wrench, ll_tau the result)
-int bmpc_plant_step(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
-                    const uint8_t* contact0, const float* wrench, float* x_next) {
+static int plant_step_host(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const float* x_fb,
+                           const float* u0, const float* foot, const uint8_t* contact0, const float* wrench, float* x_next) {
   bmpc_plant o;
   if (int rc = plant_opts(plant, &o); rc != BMPC_OK) return rc;
   if (int rc = check_batch(h, B); rc <= 0) return rc;
@@ -1204,25 +1217,56 @@ int bmpc_plant_step(bmpc_handle h, int B, const bmpc_plant* plant, const float* 
   const size_t n = (size_t)B;
   const float *d_x, *d_u0, *d_foot, *d_w;
   const uint8_t* d_c0;
+  bmpc_plant_body d_body = {nullptr, nullptr, nullptr};
   int rc = upload(h, h->stage[I_XFB], x_fb, n * IN[I_XFB].w.count(0), &d_x);
   if (rc == BMPC_OK) rc = upload(h, h->ll_u0, u0, n * 12, &d_u0);
   if (rc == BMPC_OK) rc = upload(h, h->ll_pf, foot, n * 6, &d_foot);
   if (rc == BMPC_OK) rc = upload(h, h->ll_c0, contact0, n * 2, &d_c0);
   if (rc == BMPC_OK) rc = upload(h, h->ll_q, wrench, n * 6, &d_w);
+  if (rc == BMPC_OK && body) rc = upload(h, h->body_m, body->m, n, &d_body.m);
+  if (rc == BMPC_OK && body) rc = upload(h, h->body_I, body->I, n * 9, &d_body.I);
+  if (rc == BMPC_OK && body) rc = upload(h, h->body_g, body->g, n, &d_body.g);
   if (rc != BMPC_OK) return rc;
   HIP_TRY(h->ll_tau.ensure(n * 12));
-  rc = bmpc_plant_step_device(h, B, &o, d_x, d_u0, d_foot, d_c0, d_w, h->ll_tau.p, h->stream);
+  rc = plant_step_device(h, B, &o, &d_body, d_x, d_u0, d_foot, d_c0, d_w, h->ll_tau.p, h->stream);
   if (rc != BMPC_OK) return rc;
   HIP_TRY(hipMemcpyAsync(x_next, h->ll_tau.p, n * 12 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return BMPC_OK;
 }
 
-int bmpc_simulate_device(bmpc_handle h, int B, int steps, const bmpc_plant* plant, float* x_fb, float* foot, double* t,
-                         const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push, float* u0_traj,
-                         float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any, void* stream) {
+int bmpc_plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
+                           const uint8_t* contact0, const float* wrench, float* x_next, void* stream) {
+  return plant_step_device(h, B, plant, nullptr, x_fb, u0, foot, contact0, wrench, x_next, stream);
+}
+
+int bmpc_plant_step(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
+                    const uint8_t* contact0, const float* wrench, float* x_next) {
+  return plant_step_host(h, B, plant, nullptr, x_fb, u0, foot, contact0, wrench, x_next);
+}
+
+int bmpc_plant_step_body_device(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const float* x_fb,
+                                const float* u0, const float* foot, const uint8_t* contact0, const float* wrench, float* x_next,
+                                void* stream) {
+  return plant_step_device(h, B, plant, body, x_fb, u0, foot, contact0, wrench, x_next, stream);
+}
+
+int bmpc_plant_step_body(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const float* x_fb,
+                         const float* u0, const float* foot, const uint8_t* contact0, const float* wrench, float* x_next) {
+  return plant_step_host(h, B, plant, body, x_fb, u0, foot, contact0, wrench, x_next);
+}
+
+// bmpc_simulate_device and bmpc_simulate_body_device: closed_loop() with the plant's feedback step.  Without a body and without
+// an outcome that step is simulate_feedback_kernel; else simulate_body_feedback_kernel, after the outcome arrays are initialised
+// on the stream (-1, NaN, NaN; status_any is zeroed by closed_loop the same way).
+static int simulate(bmpc_handle h, int B, int steps, const bmpc_plant* plant, const bmpc_plant_body* body, float* x_fb, float* foot,
+                    double* t, const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push, float* u0_traj,
+                    float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any, const bmpc_sim_outcome* outcome,
+                    void* stream) {
   bmpc_plant o;
   if (int rc = plant_opts(plant, &o); rc != BMPC_OK) return rc;
+  if (outcome && (outcome->tilt_max != outcome->tilt_max || outcome->z_min != outcome->z_min))
+    return fail(BMPC_ERR_INVALID, "outcome thresholds tilt_max and z_min must not be NaN");
   if (int rc = check_batch(h, B); rc < 0) return rc;
   if (steps < 0) return fail(BMPC_ERR_INVALID, "steps must be >= 0");
   if (B == 0 || steps == 0) return BMPC_OK;
@@ -1233,14 +1277,47 @@ int bmpc_simulate_device(bmpc_handle h, int B, int steps, const bmpc_plant* plan
   const bmpc::PlantParams P = plant_params(h);
   const bmpc::PlantScheme S = bmpc::plant_scheme(h->params.dt, o.integrator, o.substeps);
   const bmpc::PlantGait PG = {G.period, {G.offset[0], G.offset[1]}, {G.duty[0], G.duty[1]}, o.move_feet != 0};
+  const bool ext = has_body(body) || has_outcome(outcome);
+  const bmpc::PlantBody Bd = has_body(body) ? bmpc::PlantBody{body->m, body->I, body->g} : bmpc::PlantBody{nullptr, nullptr, nullptr};
+  bmpc::PlantOutcome O = {0.0, 0.0, nullptr, nullptr, nullptr};
+  if (has_outcome(outcome)) {
+    O = {outcome->tilt_max, outcome->z_min, outcome->first_fall, outcome->max_tilt, outcome->min_z};
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = pick_stream(h, stream);
+    if (O.first_fall) HIP_TRY(hipMemsetAsync(O.first_fall, 0xff, n * sizeof(int32_t), st));               // -1
+    if (O.max_tilt) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(O.max_tilt), 0x7fc00000, n, st));   // NaN
+    if (O.min_z) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(O.min_z), 0x7fc00000, n, st));
+  }
   return closed_loop(h, B, steps, x_fb, foot, t, gait, x_cmd, mu, status_any, stream, [&](int s, hipStream_t st) {
     const bool push_on = push && s >= o.push_from && s - o.push_from < o.push_steps;
-    hipLaunchKernelGGL(bmpc::simulate_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, P, S, PG, B, h->ro_controls.p,
-                       h->ro_contact.p, h->ro_iters.p, h->ro_status.p, push_on ? push : nullptr, x_cmd, x_fb, foot, t,
-                       u0_traj ? u0_traj + (size_t)s * n * 12 : nullptr, x_traj ? x_traj + (size_t)s * n * 12 : nullptr,
-                       foot_traj ? foot_traj + (size_t)s * n * 6 : nullptr, iters_traj ? iters_traj + (size_t)s * n : nullptr,
-                       status_any);
+    const float* w = push_on ? push : nullptr;
+    float *u0_s = u0_traj ? u0_traj + (size_t)s * n * 12 : nullptr, *x_s = x_traj ? x_traj + (size_t)s * n * 12 : nullptr,
+          *foot_s = foot_traj ? foot_traj + (size_t)s * n * 6 : nullptr;
+    int32_t* iters_s = iters_traj ? iters_traj + (size_t)s * n : nullptr;
+    if (ext)
+      hipLaunchKernelGGL(bmpc::simulate_body_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, P, Bd, O, s, S, PG, B,
+                         h->ro_controls.p, h->ro_contact.p, h->ro_iters.p, h->ro_status.p, w, x_cmd, x_fb, foot, t, u0_s, x_s, foot_s,
+                         iters_s, status_any);
+    else
+      hipLaunchKernelGGL(bmpc::simulate_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, P, S, PG, B, h->ro_controls.p,
+                         h->ro_contact.p, h->ro_iters.p, h->ro_status.p, w, x_cmd, x_fb, foot, t, u0_s, x_s, foot_s, iters_s,
+                         status_any);
   });
+}
+
+int bmpc_simulate_device(bmpc_handle h, int B, int steps, const bmpc_plant* plant, float* x_fb, float* foot, double* t,
+                         const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push, float* u0_traj,
+                         float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any, void* stream) {
+  return simulate(h, B, steps, plant, nullptr, x_fb, foot, t, gait, x_cmd, mu, push, u0_traj, x_traj, foot_traj, iters_traj, status_any,
+                  nullptr, stream);
+}
+
+int bmpc_simulate_body_device(bmpc_handle h, int B, int steps, const bmpc_plant* plant, const bmpc_plant_body* body, float* x_fb,
+                              float* foot, double* t, const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push,
+                              float* u0_traj, float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any,
+                              const bmpc_sim_outcome* outcome, void* stream) {
+  return simulate(h, B, steps, plant, body, x_fb, foot, t, gait, x_cmd, mu, push, u0_traj, x_traj, foot_traj, iters_traj, status_any,
+                  outcome, stream);
 }
 
 int bmpc_set_dispatch_order(bmpc_handle h, const int32_t* order_dev, int longest_first_rollouts) {

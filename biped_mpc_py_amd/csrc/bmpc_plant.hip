@@ -3,6 +3,8 @@
 //   plant_step               the per-instance body: values in, values out (also plain C++ for tests/emu, BMPC_EMU)
 //   plant_step_kernel        one control period of B instances (bmpc_plant_step*)
 //   simulate_feedback_kernel one closed-loop period: integrate x_fb under controls[:, 0], advance t, move landing feet, record
+//   plant_body, plant_outcome, plant_step_body_kernel, simulate_body_feedback_kernel: the same with the rigid body (m, I_b, g) taken
+//                            per instance, and each instance's fall outcome reduced over the periods (at the end of this file's parts)
 // State x = [e(3), p(3), w(3), v(3)], e = [roll, pitch, yaw], w and v in the world frame (REF:13).  Held over the period: the
 // controls u = [f1 f2 m1 m2], the feet r_0, r_1, the contact bits c_0, c_1 and an external wrench [F(3), M(3)] (world frame).
 //   R = Rz(e2) Ry(e1) Rx(e0) (REF:124-138),  I_w = R I_b R'
@@ -189,6 +191,61 @@ __device__ __forceinline__ bool plant_land(const PlantParams& P, const int k0, c
   return lands;
 }
 
+// ---- The body per instance: the PLANT's m, I_b, g of one instance in place of the handle's (one controller model, many bodies).
+
+__device__ __forceinline__ bool plant_finite(const double v) { return fabs(v) <= 1.7976931348623157e+308; }   // (false for NaN)
+
+// Pb = P with this instance's m, I9 (row-major I_b) and g, each a pointer to the instance's value or null: the handle's.
+// I_b^-1 is formed here in fp64, adjugate over determinant; without I9 it stays the handle's, bit for bit.  kv, dt, h and the
+// commands are the controller's and stay.  Returns false for a bad body: a supplied value that is not finite, m <= 0, a
+// determinant that is zero or not finite, an entry of the inverse that is not finite.
+__device__ __forceinline__ bool plant_body(const PlantParams& P, const double* m, const double* I9, const double* g, PlantParams& Pb) {
+  Pb = P;
+  bool ok = true;
+  if (m) { Pb.m = *m; ok = ok && plant_finite(Pb.m) && Pb.m > 0.0; }
+  if (g) { Pb.g = *g; ok = ok && plant_finite(Pb.g); }
+  if (I9) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { Pb.Ib[i] = I9[i]; ok = ok && plant_finite(Pb.Ib[i]); }
+    const double(&a)[9] = Pb.Ib;
+    const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
+    const double det = a[0] * c00 + a[1] * c01 + a[2] * c02, id = 1.0 / det;
+    ok = ok && plant_finite(det) && det != 0.0;
+    Pb.Ibinv[0] = c00 * id; Pb.Ibinv[1] = (a[2] * a[7] - a[1] * a[8]) * id; Pb.Ibinv[2] = (a[1] * a[5] - a[2] * a[4]) * id;
+    Pb.Ibinv[3] = c01 * id; Pb.Ibinv[4] = (a[0] * a[8] - a[2] * a[6]) * id; Pb.Ibinv[5] = (a[2] * a[3] - a[0] * a[5]) * id;
+    Pb.Ibinv[6] = c02 * id; Pb.Ibinv[7] = (a[1] * a[6] - a[0] * a[7]) * id; Pb.Ibinv[8] = (a[0] * a[4] - a[1] * a[3]) * id;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ok = ok && plant_finite(Pb.Ibinv[i]);
+  }
+  return ok;
+}
+
+// plant_step of the instance's own body; a bad body makes the next state all NaN like a bad state.
+__device__ __forceinline__ bool plant_step_body(const PlantParams& P, const double* m, const double* I9, const double* g,
+                                                const PlantScheme& S, const float (&x)[12], const float (&u)[12], const float (&r)[6],
+                                                const double c0, const double c1, const float (&w)[6], double (&xn)[12]) {
+  PlantParams Pb;
+  bool ok = plant_body(P, m, I9, g, Pb);
+  ok = plant_step(Pb, S, x, u, r, c0, c1, w, xn) && ok;
+  if (!ok) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) xn[i] = __builtin_nan("");
+  }
+  return ok;
+}
+
+// The fall outcome of one instance, reduced over the periods: x is the state after period s as stored (fp32).  Fallen at s iff
+// !(|x0| <= tilt_max && |x1| <= tilt_max && x5 >= z_min), the fp32 values widened against the fp64 thresholds, so that a NaN
+// state counts as fallen.  first_fall: the first such s (-1 so far: none); max_tilt, min_z: the extrema of max(|x0|, |x1|) and
+// of x5 over the periods that are not NaN (fmaxf / fminf from a NaN start).
+__device__ __forceinline__ void plant_outcome(const double tilt_max, const double z_min, const float (&x)[12], const int s,
+                                              int32_t& first_fall, float& max_tilt, float& min_z) {
+  const bool up = fabs((double)x[0]) <= tilt_max && fabs((double)x[1]) <= tilt_max && (double)x[5] >= z_min;
+  if (!up && first_fall < 0) first_fall = s;
+  max_tilt = fmaxf(max_tilt, fmaxf(fabsf(x[0]), fabsf(x[1])));
+  min_z = fminf(min_z, x[5]);
+}
+
 }  // namespace bmpc
 
 #ifndef BMPC_EMU
@@ -292,6 +349,136 @@ simulate_feedback_kernel(const PlantParams P, const PlantScheme S, const PlantGa
 #pragma unroll
     for (int i = 0; i < 6; ++i) foot_out[(size_t)b * 6 + i] = rf[i];
   }
+}
+
+
+// the per-instance body as the kernels get it: m [B], I [B][9] row-major, g [B], each null for the handle's value
+struct PlantBody { const double *m, *I, *g; };
+// the fall outcome of bmpc_simulate_body_device: thresholds, first_fall [B], max_tilt [B], min_z [B] (each null: not wanted)
+struct PlantOutcome { double tilt_max, z_min; int32_t* first_fall; float *max_tilt, *min_z; };
+
+// One instance of plant_step_body_kernel: plant_step_kernel's with the body from Bd.
+__device__ __forceinline__ void plant_step_body_instance(const PlantParams& P, const PlantBody& Bd, const PlantScheme& S, const int b,
+                                                    const float* __restrict__ x_fb, const float* __restrict__ u0,
+                                                    const float* __restrict__ foot, const uint8_t* __restrict__ contact0,
+                                                    const float* __restrict__ wrench, float* __restrict__ x_next) {
+  float x[12], u[12], r[6], w[6];
+  double xn[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { x[i] = x_fb[(size_t)b * 12 + i]; u[i] = u0[(size_t)b * 12 + i]; }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { r[i] = foot[(size_t)b * 6 + i]; w[i] = wrench ? wrench[(size_t)b * 6 + i] : 0.f; }
+  const double c0 = contact0[(size_t)b * 2] ? 1.0 : 0.0, c1 = contact0[(size_t)b * 2 + 1] ? 1.0 : 0.0;
+  plant_step_body(P, Bd.m ? Bd.m + b : nullptr, Bd.I ? Bd.I + (size_t)b * 9 : nullptr, Bd.g ? Bd.g + b : nullptr, S, x, u, r, c0, c1, w, xn);
+#pragma unroll
+  for (int i = 0; i < 12; ++i) x_next[(size_t)b * 12 + i] = (float)xn[i];
+}
+
+// One instance of simulate_body_feedback_kernel: simulate_feedback_kernel's period, statement for statement, with the body from Bd
+// and the outcome O of period s reduced where it is asked for.  (Written out a second time on purpose: the two kernels above are
+// held to their instruction sequence, and routed through a shared function they compile to another one, with spills.)
+__device__ __forceinline__ void feedback_body_instance(const PlantParams& P, const PlantBody& Bd, const PlantOutcome& O, const int s,
+                                                  const PlantScheme& S, const PlantGait& G, const int b,
+                                                  const float* __restrict__ controls, const uint8_t* __restrict__ contact,
+                                                  const int32_t* __restrict__ iters, const int32_t* __restrict__ status,
+                                                  const float* __restrict__ push, const float* __restrict__ x_cmd,
+                                                  float* __restrict__ x_fb, float* foot, double* __restrict__ t,
+                                                  float* __restrict__ u0_out, float* __restrict__ x_out, float* __restrict__ foot_out,
+                                                  int32_t* __restrict__ iters_out, int32_t* __restrict__ status_any) {
+  const int h = (int)P.h;
+  const float* u0 = controls + (size_t)b * h * 12;
+  float x[12], u[12], r[6], w[6];
+  double xn[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { x[i] = x_fb[(size_t)b * 12 + i]; u[i] = u0[i]; }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { r[i] = foot[(size_t)b * 6 + i]; w[i] = push ? push[(size_t)b * 6 + i] : 0.f; }
+  // What does not depend on the step comes first (the applied control, the iteration count, the solver's status): behind the
+  // step, its loads are hoisted above the stages and sit in registers there.
+  if (u0_out) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) u0_out[(size_t)b * 12 + i] = u[i];
+  }
+  if (iters_out) iters_out[b] = iters[b];
+  if (status_any) status_any[b] |= status[b];
+  const uint8_t* row0 = contact + (size_t)b * h * 2;
+  const bool ok = plant_step_body(P, Bd.m ? Bd.m + b : nullptr, Bd.I ? Bd.I + (size_t)b * 9 : nullptr, Bd.g ? Bd.g + b : nullptr, S, x,
+                                  u, r, row0[0] ? 1.0 : 0.0, row0[1] ? 1.0 : 0.0, w, xn);
+  if (!ok && status_any) status_any[b] |= 2;      // BMPC_NUMERICAL
+  float xf[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    xf[i] = (float)xn[i];
+    x_fb[(size_t)b * 12 + i] = xf[i];
+    if (x_out) x_out[(size_t)b * 12 + i] = xf[i];
+  }
+  if (O.first_fall || O.max_tilt || O.min_z) {
+    // (the entry initialised the three arrays on the stream: -1, NaN, NaN)
+    int32_t first = O.first_fall ? O.first_fall[b] : 0;
+    float mt = O.max_tilt ? O.max_tilt[b] : 0.f, mz = O.min_z ? O.min_z[b] : 0.f;
+    plant_outcome(O.tilt_max, O.z_min, xf, s, first, mt, mz);
+    if (O.first_fall) O.first_fall[b] = first;
+    if (O.max_tilt) O.max_tilt[b] = mt;
+    if (O.min_z) O.min_z[b] = mz;
+  }
+  const double t0 = t[b], t1 = t0 + P.dt;
+  t[b] = t1;
+  // the schedule steps of t0 and t1, as gait_kernel finds them (REF:56-57)
+  double ka = fmod(py_floordiv(t0, P.dt), P.h), kb = fmod(py_floordiv(t1, P.dt), P.h);
+  if (ka < 0) ka += P.h;
+  if (kb < 0) kb += P.h;
+  const int k0 = (int)ka, k1 = (int)kb;
+  float rf[6];                                   // (`foot` is not __restrict__: read again here, not carried through the stages)
+#pragma unroll
+  for (int i = 0; i < 6; ++i) rf[i] = foot[(size_t)b * 6 + i];
+  if (G.move_feet) {
+    // the target is taken at the fp32 state the next solve will see
+    double xs[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) xs[i] = xf[i];
+    const double cx = x_cmd ? (double)x_cmd[(size_t)b * 12 + 3] : P.cmd_x, cy = x_cmd ? (double)x_cmd[(size_t)b * 12 + 4] : P.cmd_y;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      double rg[3];
+      if (plant_land(P, k0, k1, G.offset[g], G.period, G.duty[g], g == 0 ? 1.0 : -1.0, xs, cx, cy, rg)) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          rf[3 * g + i] = (float)rg[i];
+          foot[(size_t)b * 6 + 3 * g + i] = rf[3 * g + i];
+        }
+      }
+    }
+  }
+  if (foot_out) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) foot_out[(size_t)b * 6 + i] = rf[i];
+  }
+}
+
+// The two kernels above with the body per instance (Bd: m, I_b, g of each instance where given, plant_body) and, in the closed
+// loop, the outcome of period s reduced into O.  Eighteen more values per thread (I_b, I_b^-1) live in vector registers here
+// where the handle's sit in scalar ones: three waves per SIMD (168 registers) instead of four.
+__global__ void __launch_bounds__(256, 3)
+plant_step_body_kernel(const PlantParams P, const PlantBody Bd, const PlantScheme S, const int B, const float* __restrict__ x_fb,
+                       const float* __restrict__ u0, const float* __restrict__ foot, const uint8_t* __restrict__ contact0,
+                       const float* __restrict__ wrench, float* __restrict__ x_next) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  plant_step_body_instance(P, Bd, S, b, x_fb, u0, foot, contact0, wrench, x_next);
+}
+
+__global__ void __launch_bounds__(256, 3)
+simulate_body_feedback_kernel(const PlantParams P, const PlantBody Bd, const PlantOutcome O, const int s, const PlantScheme S,
+                              const PlantGait G, const int B, const float* __restrict__ controls,
+                              const uint8_t* __restrict__ contact, const int32_t* __restrict__ iters,
+                              const int32_t* __restrict__ status, const float* __restrict__ push, const float* __restrict__ x_cmd,
+                              float* __restrict__ x_fb, float* foot, double* __restrict__ t, float* __restrict__ u0_out,
+                              float* __restrict__ x_out, float* __restrict__ foot_out, int32_t* __restrict__ iters_out,
+                              int32_t* __restrict__ status_any) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  feedback_body_instance(P, Bd, O, s, S, G, b, controls, contact, iters, status, push, x_cmd, x_fb, foot, t, u0_out, x_out, foot_out,
+                          iters_out, status_any);
 }
 
 }  // namespace bmpc

@@ -602,6 +602,51 @@ int bmpc_simulate_device(bmpc_handle h, int B, int steps, const bmpc_plant* plan
                          float* u0_traj, float* x_traj, float* foot_traj,
                          int32_t* iters_traj, int32_t* status_any, void* stream);
 
+/*
+ * The plant with a body per instance, and the fall outcome of a simulation (added under ABI 13 like the entries above: detect
+ * them by the symbol).  The entries above integrate the body the controller believes in: m, I, g of the handle's bmpc_params.
+ * These take the PLANT's m, I and g per instance, so that one launch sequence answers what one controller model makes of
+ * thousands of real bodies (a payload, a wrong inertia estimate, another gravity).  Everything that is the controller's stays the
+ * handle's: the solve inside the loop reads the handle's parameter block as before, and kv, dt, h, the commands and the landing
+ * rule are untouched.  There is no centre-of-mass offset (the lever arms still run from p), there are no per-instance controller
+ * parameters, and an instance that has fallen keeps being solved and integrated.
+ *   bmpc_plant_body   m [B], I [B][9] (row-major body inertia, any invertible matrix), g [B], fp64; a NULL member is the handle's
+ *                     value.  I^-1 is formed per instance in fp64 (adjugate over determinant).  A bad body -- a non-finite value,
+ *                     m <= 0, a determinant that is zero or non-finite, a non-finite entry of the inverse -- makes the next state of
+ *                     that instance all NaN (in the closed loop: BMPC_NUMERICAL in status_any), like a bad state; no other instance
+ *                     is touched.  `body` NULL, or all three members NULL: the entries above, bit for bit.
+ *   bmpc_sim_outcome  per instance, reduced over the periods on the device.  An instance has FALLEN at period s iff
+ *                     !(|x[0]| <= tilt_max && |x[1]| <= tilt_max && x[5] >= z_min) at the state stored after period s (fp32, widened
+ *                     to fp64 for the comparison): a NaN state counts as fallen.  first_fall [B]: the smallest such s, or -1;
+ *                     max_tilt [B]: the maximum over the periods of max(|x[0]|, |x[1]|); min_z [B]: the minimum of x[5]; both fp32,
+ *                     over the periods whose value is not NaN, NaN if there is none.  The entry initialises the arrays on the
+ *                     stream.  Each array may be NULL; `outcome` NULL or all three NULL: nothing is reduced.  A NaN threshold is
+ *                     BMPC_ERR_INVALID (checked with the plant block, before the handle); +inf / -inf switch a threshold off.
+ *   bmpc_plant_step_body_device / bmpc_plant_step_body   bmpc_plant_step_device / bmpc_plant_step with `body` (DEVICE / HOST
+ *                     pointers, `body` members included)
+ *   bmpc_simulate_body_device   bmpc_simulate_device with `body` (DEVICE pointers) and `outcome`; the same loop, another feedback step
+ */
+typedef struct bmpc_plant_body {      /* per-instance rigid body of the PLANT; each member NULL -> the handle's value */
+  const double* m;                    /* [B]    */
+  const double* I;                    /* [B][9] body inertia, row-major, any invertible matrix */
+  const double* g;                    /* [B]    */
+} bmpc_plant_body;
+typedef struct bmpc_sim_outcome {
+  double tilt_max, z_min;             /* NaN: BMPC_ERR_INVALID; +inf / -inf allowed */
+  int32_t* first_fall;                /* [B] or NULL */
+  float* max_tilt;                    /* [B] or NULL */
+  float* min_z;                       /* [B] or NULL */
+} bmpc_sim_outcome;
+int bmpc_plant_step_body_device(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const float* x_fb,
+                                const float* u0, const float* foot, const uint8_t* contact0, const float* wrench, float* x_next,
+                                void* stream);
+int bmpc_plant_step_body(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const float* x_fb,
+                         const float* u0, const float* foot, const uint8_t* contact0, const float* wrench, float* x_next);
+int bmpc_simulate_body_device(bmpc_handle h, int B, int steps, const bmpc_plant* plant, const bmpc_plant_body* body, float* x_fb,
+                              float* foot, double* t, const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push,
+                              float* u0_traj, float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any,
+                              const bmpc_sim_outcome* outcome, void* stream);
+
 /* Diagnostics: when device_buf (DEVICE pointer, [max_batch][16] int64) is non-NULL every later solve
  * writes per-instance shader-clock stamps {setup, block algebra, dense sweeps, total, iters,
  * factorisations, -, -, iteration phases P0..P5, stop test + adaptation, -}; NULL switches it off
