@@ -28,6 +28,7 @@ EXPORTS = (
     "bmpc_set_warm_start", "bmpc_reset_warm_start", "bmpc_rollout_device", "bmpc_set_dispatch_order",
     "bmpc_plant_default", "bmpc_plant_step", "bmpc_plant_step_device", "bmpc_simulate_device",
     "bmpc_plant_step_body", "bmpc_plant_step_body_device", "bmpc_simulate_body_device",
+    "bmpc_plant_step_ground", "bmpc_plant_step_ground_device", "bmpc_simulate_ground_device",
 )
 
 
@@ -53,6 +54,17 @@ class CSimOutcome(C.Structure):
     """`bmpc_sim_outcome` of include/bmpc.h: the fall thresholds and the per-instance outcome arrays (NULL: not wanted)."""
     _fields_ = [("tilt_max", C.c_double), ("z_min", C.c_double), ("first_fall", C.c_void_p), ("max_tilt", C.c_void_p),
                 ("min_z", C.c_void_p)]
+
+
+class CPlantGround(C.Structure):
+    """`bmpc_plant_ground` of include/bmpc.h: the true friction mu [B][2] per leg (NULL: the handle's mu for both legs)."""
+    _fields_ = [("mu", C.c_void_p)]
+
+
+class CGroundOut(C.Structure):
+    """`bmpc_ground_out` of include/bmpc.h: the floor of the demand and what the closed loop records of the ground (NULL: not wanted)."""
+    _fields_ = [("fz_floor", C.c_double)] + [(n, C.c_void_p) for n in ("u_applied", "flags", "first_slip", "slip_periods",
+                                                                     "unloaded_periods", "mu_demand")]
 
 
 class CHostViews(C.Structure):
@@ -196,6 +208,10 @@ def load():
     lib.bmpc_plant_step_body_device.argtypes = [vp, ip, C.POINTER(CPlant), C.POINTER(CPlantBody)] + [vp] * 7
     lib.bmpc_simulate_body_device.argtypes = [vp, ip, ip, C.POINTER(CPlant), C.POINTER(CPlantBody), vp, vp, vp, C.POINTER(CGait)] + \
         [vp] * 8 + [C.POINTER(CSimOutcome), vp]
+    lib.bmpc_plant_step_ground.argtypes = [vp, ip, C.POINTER(CPlant), C.POINTER(CPlantBody), C.POINTER(CPlantGround)] + [vp] * 8
+    lib.bmpc_plant_step_ground_device.argtypes = [vp, ip, C.POINTER(CPlant), C.POINTER(CPlantBody), C.POINTER(CPlantGround)] + [vp] * 9
+    lib.bmpc_simulate_ground_device.argtypes = [vp, ip, ip, C.POINTER(CPlant), C.POINTER(CPlantBody), C.POINTER(CPlantGround), vp, vp,
+                                                vp, C.POINTER(CGait)] + [vp] * 8 + [C.POINTER(CSimOutcome), C.POINTER(CGroundOut), vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name != "bmpc_last_error":

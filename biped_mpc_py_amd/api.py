@@ -734,14 +734,57 @@ class BatchSolver:
             setattr(cb, k, v.data_ptr())
         return cb
 
-    def plant_step(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4, body=None):
+    @staticmethod
+    def _ground_mu(ground, want_applied=False):
+        """The `mu` of a `ground` mapping, or None ({}: the handle's mu); anything but a mapping whose only key is 'mu', or
+        `want_applied` without a ground, is a ValueError."""
+        if ground is None:
+            if want_applied:
+                raise ValueError("want_applied needs a ground")
+            return None
+        if not hasattr(ground, "keys") or set(ground.keys()) - {"mu"}:
+            raise ValueError("ground must be a mapping whose only key is 'mu'")
+        return ground.get("mu")
+
+    @classmethod
+    def _ground_host(cls, ground, B):
+        """(`bmpc_plant_ground` of a host array, the array it points into) from a `ground` mapping: mu float64 (B, 2) or absent."""
+        cg, mu = _lib.CPlantGround(), cls._ground_mu(ground)
+        if mu is not None:
+            mu = np.asarray(mu)
+            if mu.dtype != np.float64 or mu.shape != (B, 2):
+                raise ValueError(f"ground['mu'] must be float64 of shape {(B, 2)}, not {mu.dtype} {mu.shape}")
+            mu = np.ascontiguousarray(mu)
+            cg.mu = mu.ctypes.data
+        return cg, mu
+
+    @classmethod
+    def _ground_device(cls, ground, B, dev):
+        """`bmpc_plant_ground` of a device pointer from a `ground` mapping: mu a contiguous float64 tensor (B, 2) on `dev`, or absent."""
+        import torch
+        cg, mu = _lib.CPlantGround(), cls._ground_mu(ground)
+        if mu is not None:
+            if not isinstance(mu, torch.Tensor) or mu.dtype != torch.float64 or mu.device != dev or not mu.is_contiguous() \
+                    or tuple(mu.shape) != (B, 2):
+                raise ValueError(f"ground['mu'] must be a contiguous float64 tensor on {dev} of shape {(B, 2)}")
+            cg.mu = mu.data_ptr()
+        return cg
+
+    def plant_step(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4, body=None, ground=None,
+                   want_applied=False):
         """One control period of the plant -- the nonlinear single rigid body of include/bmpc.h, NOT the controller's linear model --
         under held controls (`bmpc_plant_step`): x_fb (B,12), u0 (B,12) = [f1 f2 m1 m2], foot (B,6), contact0 (B,2) (a leg with bit 0
         transmits nothing), wrench (B,6) = [F, M] in the world frame or None -> x_next (B,12) fp64.  A bad instance (non-finite input,
         pitch at +-90 degrees) comes back all NaN.  `body`: a mapping with any of m (B,), I (B,3,3) or (B,9), g (B,) as float64
         arrays -- the PLANT's mass, body inertia and gravity per instance in place of this solver's (`bmpc_plant_step_body`); a bad
-        body (non-finite, m <= 0, singular I) comes back all NaN too."""
+        body (non-finite, m <= 0, singular I) comes back all NaN too.
+        `ground`: a mapping whose only allowed key is mu, float64 (B,2) -- the true friction under each leg; {} means this solver's
+        mu.  A flat floor with Coulomb friction then stands between u0 and the body (`bmpc_plant_step_ground`): a stance leg with
+        fz <= 0 transmits nothing (flag 4 << leg), a loaded one whose tangential force exceeds mu fz has it scaled onto the cone
+        (flag 1 << leg); a mu that is NaN or negative comes back all NaN.  With `want_applied` the result is (x_next, u_applied
+        (B,12) float32 -- what reached the body --, flags (B,) uint8)."""
         plant = self._plant(integrator, substeps)
+        self._ground_mu(ground, want_applied)
         a = np.asarray(x_fb, np.float32)
         if a.ndim != 2 or a.shape[1] != 12:
             raise ValueError(f"x_fb must have shape (B, 12), not {a.shape}")
@@ -757,6 +800,14 @@ class BatchSolver:
                 raise ValueError(f"{name} must have shape {shp}, not {v.shape}")
             arrs.append(np.ascontiguousarray((v != 0).astype(np.uint8) if dt is None else v.astype(dt)))
         out = np.empty((B, 12), np.float32)
+        if ground is not None:
+            cg, keep_g = self._ground_host(ground, B)
+            cb, keep = (None, None) if body is None else self._body_host(body, B)
+            ua, fl = (np.empty((B, 12), np.float32), np.empty(B, np.uint8)) if want_applied else (None, None)
+            _lib.check(self._lib.bmpc_plant_step_ground(self._h, B, C.byref(plant), None if cb is None else C.byref(cb), C.byref(cg),
+                                                        *[_ptr(v) for v in arrs], _ptr(out), _ptr(ua), _ptr(fl)))
+            del keep, keep_g
+            return (out.astype(np.float64), ua, fl) if want_applied else out.astype(np.float64)
         if body is None:
             _lib.check(self._lib.bmpc_plant_step(self._h, B, C.byref(plant), *[_ptr(v) for v in arrs], _ptr(out)))
         else:
@@ -766,13 +817,15 @@ class BatchSolver:
         return out.astype(np.float64)
 
     def plant_step_device(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4, x_next=None, stream=None,
-                          body=None):
+                          body=None, ground=None, want_applied=False):
         """`plant_step` on device tensors (`bmpc_plant_step_device`): float32 x_fb (B,12), u0 (B,12), foot (B,6), uint8 contact0 (B,2),
         float32 wrench (B,6) or None -> x_next (B,12) float32 (allocated unless given).  `body`: as for `plant_step`, of float64
-        tensors on the device (`bmpc_plant_step_body_device`).  Asynchronous on `stream` (default: torch's current stream); nothing
-        crosses PCIe."""
+        tensors on the device (`bmpc_plant_step_body_device`).  `ground`, `want_applied`: as for `plant_step`, mu a float64 tensor
+        (B,2) on the device (`bmpc_plant_step_ground_device`); with `want_applied` the result is (x_next, u_applied (B,12) float32,
+        flags (B,) uint8).  Asynchronous on `stream` (default: torch's current stream); nothing crosses PCIe."""
         import torch
         plant = self._plant(integrator, substeps)
+        self._ground_mu(ground, want_applied)
         dev = x_fb.device
         if dev.type != "cuda" or dev.index != self.device:
             raise ValueError(f"tensors must live on cuda:{self.device}")
@@ -786,6 +839,14 @@ class BatchSolver:
                 _tensor_ptr(foot, torch.float32, (B, 6), dev), _tensor_ptr(contact0, torch.uint8, (B, 2), dev),
                 _tensor_ptr(wrench, torch.float32, (B, 6), dev), _tensor_ptr(x_next, torch.float32, (B, 12), dev)]
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        if ground is not None:
+            cg = self._ground_device(ground, B, dev)
+            ua = torch.empty((B, 12), dtype=torch.float32, device=dev) if want_applied else None
+            fl = torch.empty((B,), dtype=torch.uint8, device=dev) if want_applied else None
+            _lib.check(self._lib.bmpc_plant_step_ground_device(
+                self._h, B, C.byref(plant), None if cb is None else C.byref(cb), C.byref(cg), *args,
+                None if ua is None else ua.data_ptr(), None if fl is None else fl.data_ptr(), st))
+            return (x_next, ua, fl) if want_applied else x_next
         if cb is None:
             _lib.check(self._lib.bmpc_plant_step_device(self._h, B, C.byref(plant), *args, st))
         else:
@@ -794,7 +855,7 @@ class BatchSolver:
 
     def simulate_device(self, x_fb, foot, t, steps, x_cmd=None, mu=None, period=None, offset=None, duty=None, integrator="rk4",
                         substeps=4, move_feet=True, push=None, push_from=0, push_steps=0, want_iters=True, stream=None, body=None,
-                        fall=None):
+                        fall=None, ground=None, fz_floor=0.0):
         """`steps` closed-loop control periods against the plant of `plant_step` (`bmpc_simulate_device`): `rollout_device`'s loop
         with the rigid body in place of the controller's own prediction.  x_fb (B,12) float32, foot (B,6) float32 and t (B,) float64
         are advanced IN PLACE (so `foot` must be writable): with `move_feet` a leg that lands gets the swing controller's foothold
@@ -805,9 +866,19 @@ class BatchSolver:
         solver's) -- the controller inside the loop keeps this solver's model: one model, many bodies (`bmpc_simulate_body_device`).
         `fall` = (tilt_max, z_min): the dict also carries first_fall (B,) int32 -- the first period after which
         !(|roll| <= tilt_max and |pitch| <= tilt_max and p_z >= z_min), a NaN state included, or -1 --, max_tilt (B,) and min_z (B,)
-        float32, the extrema of max(|roll|, |pitch|) and p_z over the periods that are not NaN.  Fallen instances run on."""
+        float32, the extrema of max(|roll|, |pitch|) and p_z over the periods that are not NaN.  Fallen instances run on.
+        `ground`: a mapping whose only allowed key is mu, a float64 device tensor (B,2) -- the TRUE friction under each leg; {} means
+        this solver's mu (`bmpc_simulate_ground_device`).  The `mu` argument stays the controller's belief.  The plant integrates
+        what the ground transmits of each command (see `plant_step`), u0 keeps recording the command, and the dict also carries
+        u_applied (steps,B,12) float32, contact_flags (steps,B) uint8 (1, 2: leg 0 / 1 slipped; 4, 8: unloaded), first_slip (B,)
+        int32 -- the first period with a slip, or -1 --, slip_periods and unloaded_periods (B,2) int32, and mu_demand (B,) float32:
+        the largest tangential over normal force any loaded leg with fz >= `fz_floor` asked for, NaN if none did.  A slipping foot
+        keeps its foothold."""
         import torch
         plant = self._plant(integrator, substeps, move_feet, push_from, push_steps)
+        self._ground_mu(ground)
+        if ground is not None and not float(fz_floor) >= 0.0:
+            raise ValueError("fz_floor must be >= 0 and not NaN")
         if fall is not None:
             try:
                 tilt_max, z_min = (float(v) for v in fall)
@@ -835,7 +906,7 @@ class BatchSolver:
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
         out = dict(u0=u0, x=xt, foot=ft, iters=its, status_any=st_any)
         traj = [u0.data_ptr(), xt.data_ptr(), ft.data_ptr(), None if its is None else its.data_ptr(), st_any.data_ptr()]
-        if cb is None and fall is None:
+        if cb is None and fall is None and ground is None:
             _lib.check(self._lib.bmpc_simulate_device(
                 self._h, B, steps, C.byref(plant), *args, None if gait is None else C.byref(gait), *opt, *traj, st))
             return out
@@ -846,6 +917,21 @@ class BatchSolver:
                        max_tilt=torch.full((B,), float("nan"), dtype=torch.float32, device=dev),
                        min_z=torch.full((B,), float("nan"), dtype=torch.float32, device=dev))
             co = _lib.CSimOutcome(tilt_max, z_min, out["first_fall"].data_ptr(), out["max_tilt"].data_ptr(), out["min_z"].data_ptr())
+        if ground is not None:
+            cg = self._ground_device(ground, B, dev)
+            # (the reduced arrays filled here as the entry does it, like the outcome's)
+            out.update(u_applied=torch.empty((steps, B, 12), dtype=torch.float32, device=dev),
+                       contact_flags=torch.empty((steps, B), dtype=torch.uint8, device=dev),
+                       first_slip=torch.full((B,), -1, dtype=torch.int32, device=dev),
+                       slip_periods=torch.zeros((B, 2), dtype=torch.int32, device=dev),
+                       unloaded_periods=torch.zeros((B, 2), dtype=torch.int32, device=dev),
+                       mu_demand=torch.full((B,), float("nan"), dtype=torch.float32, device=dev))
+            go = _lib.CGroundOut(float(fz_floor), *[out[k].data_ptr() for k in ("u_applied", "contact_flags", "first_slip", "slip_periods",
+                                                                                "unloaded_periods", "mu_demand")])
+            _lib.check(self._lib.bmpc_simulate_ground_device(
+                self._h, B, steps, C.byref(plant), None if cb is None else C.byref(cb), C.byref(cg), *args,
+                None if gait is None else C.byref(gait), *opt, *traj, None if co is None else C.byref(co), C.byref(go), st))
+            return out
         _lib.check(self._lib.bmpc_simulate_body_device(
             self._h, B, steps, C.byref(plant), None if cb is None else C.byref(cb), *args, None if gait is None else C.byref(gait), *opt,
             *traj, None if co is None else C.byref(co), st))

@@ -233,6 +233,9 @@ struct bmpc_handle_s {
   DevBuf<double> ll_t;
   DevBuf<uint8_t> ll_c0;
   DevBuf<double> body_m, body_I, body_g;   // bmpc_plant_step_body: the host body on the device
+  DevBuf<double> ground_mu;                // bmpc_plant_step_ground: the host ground on the device, and what it records on its way back
+  DevBuf<float> ground_ua;
+  DevBuf<uint8_t> ground_fl;
   long long* prof_dev = nullptr;   // optional cycle-stamp buffer (bmpc_debug_set_profile)
   // receding-horizon warm start (bmpc_set_warm_start): solver state of the last batch, kept on the device
   DevBuf<double> warm;
@@ -1183,21 +1186,35 @@ static bmpc::PlantParams plant_params(bmpc_handle h) {
 // whether a body / an outcome asks for anything: without, the entries run the kernels of the handle's own body
 static bool has_body(const bmpc_plant_body* b) { return b && (b->m || b->I || b->g); }
 static bool has_outcome(const bmpc_sim_outcome* o) { return o && (o->first_fall || o->max_tilt || o->min_z); }
+static bool has_ground_sum(const bmpc_ground_out* o) { return o && (o->first_slip || o->slip_periods || o->unloaded_periods || o->mu_demand); }
 
-// bmpc_plant_step_device and bmpc_plant_step_body_device: `body` null or empty launches plant_step_kernel
-static int plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const float* x_fb,
-                             const float* u0, const float* foot, const uint8_t* contact0, const float* wrench, float* x_next,
-                             void* stream) {
+// what a ground entry is asked to record without a ground to record it of; host logic only, checked with the plant block
+static int ground_opts(const bmpc_plant_ground* ground, const void* u_applied, const void* flags, const bmpc_ground_out* gout) {
+  if (gout && !(gout->fz_floor >= 0.0)) return fail(BMPC_ERR_INVALID, "fz_floor must be >= 0 and not NaN");
+  if (!ground && (u_applied || flags || gout)) return fail(BMPC_ERR_INVALID, "u_applied, flags and gout need a ground");
+  return BMPC_OK;
+}
+
+// bmpc_plant_step_device, bmpc_plant_step_body_device and bmpc_plant_step_ground_device: without a ground, `body` null or empty
+// launches plant_step_kernel; with a ground (its mu null: the handle's) plant_step_ground_kernel, whatever the body
+static int plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                             const float* x_fb, const float* u0, const float* foot, const uint8_t* contact0, const float* wrench,
+                             float* x_next, float* u_applied, uint8_t* flags, void* stream) {
   bmpc_plant o;
   if (int rc = plant_opts(plant, &o); rc != BMPC_OK) return rc;
+  if (int rc = ground_opts(ground, u_applied, flags, nullptr); rc != BMPC_OK) return rc;
   if (int rc = check_batch(h, B); rc <= 0) return rc;
   if (!x_fb || !u0 || !foot || !contact0 || !x_next) return fail(BMPC_ERR_INVALID, "x_fb, u0, foot, contact0 and x_next must be non-null");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = pick_stream(h, stream);
   const bmpc::PlantScheme S = bmpc::plant_scheme(h->params.dt, o.integrator, o.substeps);
-  if (has_body(body))
-    hipLaunchKernelGGL(bmpc::plant_step_body_kernel, dim3((B + 255) / 256), dim3(256), 0, st, plant_params(h),
-                       bmpc::PlantBody{body->m, body->I, body->g}, S, B, x_fb, u0, foot, contact0, wrench, x_next);
+  const bmpc::PlantBody Bd = has_body(body) ? bmpc::PlantBody{body->m, body->I, body->g} : bmpc::PlantBody{nullptr, nullptr, nullptr};
+  if (ground)
+    hipLaunchKernelGGL(bmpc::plant_step_ground_kernel, dim3((B + 255) / 256), dim3(256), 0, st, plant_params(h), Bd,
+                       bmpc::PlantGround{ground->mu, h->params.mu, u_applied, flags}, S, B, x_fb, u0, foot, contact0, wrench, x_next);
+  else if (has_body(body))
+    hipLaunchKernelGGL(bmpc::plant_step_body_kernel, dim3((B + 255) / 256), dim3(256), 0, st, plant_params(h), Bd, S, B, x_fb, u0,
+                       foot, contact0, wrench, x_next);
   else
     hipLaunchKernelGGL(bmpc::plant_step_kernel, dim3((B + 255) / 256), dim3(256), 0, st, plant_params(h), S, B, x_fb, u0, foot,
                        contact0, wrench, x_next);
@@ -1205,12 +1222,14 @@ static int plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, cons
   return BMPC_OK;
 }
 
-// bmpc_plant_step and bmpc_plant_step_body
+// bmpc_plant_step, bmpc_plant_step_body and bmpc_plant_step_ground
 // (staging: the buffers of the low-level host entries -- ll_pf holds foot positions there too; ll_q the wrench, ll_tau the result)
-static int plant_step_host(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const float* x_fb,
-                           const float* u0, const float* foot, const uint8_t* contact0, const float* wrench, float* x_next) {
+static int plant_step_host(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                           const float* x_fb, const float* u0, const float* foot, const uint8_t* contact0, const float* wrench,
+                           float* x_next, float* u_applied, uint8_t* flags) {
   bmpc_plant o;
   if (int rc = plant_opts(plant, &o); rc != BMPC_OK) return rc;
+  if (int rc = ground_opts(ground, u_applied, flags, nullptr); rc != BMPC_OK) return rc;
   if (int rc = check_batch(h, B); rc <= 0) return rc;
   if (!x_fb || !u0 || !foot || !contact0 || !x_next) return fail(BMPC_ERR_INVALID, "x_fb, u0, foot, contact0 and x_next must be non-null");
   HIP_TRY(hipSetDevice(h->device));
@@ -1218,6 +1237,7 @@ static int plant_step_host(bmpc_handle h, int B, const bmpc_plant* plant, const 
   const float *d_x, *d_u0, *d_foot, *d_w;
   const uint8_t* d_c0;
   bmpc_plant_body d_body = {nullptr, nullptr, nullptr};
+  bmpc_plant_ground d_ground = {nullptr};
   int rc = upload(h, h->stage[I_XFB], x_fb, n * IN[I_XFB].w.count(0), &d_x);
   if (rc == BMPC_OK) rc = upload(h, h->ll_u0, u0, n * 12, &d_u0);
   if (rc == BMPC_OK) rc = upload(h, h->ll_pf, foot, n * 6, &d_foot);
@@ -1226,47 +1246,69 @@ static int plant_step_host(bmpc_handle h, int B, const bmpc_plant* plant, const 
   if (rc == BMPC_OK && body) rc = upload(h, h->body_m, body->m, n, &d_body.m);
   if (rc == BMPC_OK && body) rc = upload(h, h->body_I, body->I, n * 9, &d_body.I);
   if (rc == BMPC_OK && body) rc = upload(h, h->body_g, body->g, n, &d_body.g);
+  if (rc == BMPC_OK && ground) rc = upload(h, h->ground_mu, ground->mu, n * 2, &d_ground.mu);
   if (rc != BMPC_OK) return rc;
   HIP_TRY(h->ll_tau.ensure(n * 12));
-  rc = plant_step_device(h, B, &o, &d_body, d_x, d_u0, d_foot, d_c0, d_w, h->ll_tau.p, h->stream);
+  if (u_applied) HIP_TRY(h->ground_ua.ensure(n * 12));
+  if (flags) HIP_TRY(h->ground_fl.ensure(n));
+  rc = plant_step_device(h, B, &o, &d_body, ground ? &d_ground : nullptr, d_x, d_u0, d_foot, d_c0, d_w, h->ll_tau.p,
+                         u_applied ? h->ground_ua.p : nullptr, flags ? h->ground_fl.p : nullptr, h->stream);
   if (rc != BMPC_OK) return rc;
   HIP_TRY(hipMemcpyAsync(x_next, h->ll_tau.p, n * 12 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (u_applied) HIP_TRY(hipMemcpyAsync(u_applied, h->ground_ua.p, n * 12 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (flags) HIP_TRY(hipMemcpyAsync(flags, h->ground_fl.p, n, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return BMPC_OK;
 }
 
 int bmpc_plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
                            const uint8_t* contact0, const float* wrench, float* x_next, void* stream) {
-  return plant_step_device(h, B, plant, nullptr, x_fb, u0, foot, contact0, wrench, x_next, stream);
+  return plant_step_device(h, B, plant, nullptr, nullptr, x_fb, u0, foot, contact0, wrench, x_next, nullptr, nullptr, stream);
 }
 
 int bmpc_plant_step(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
                     const uint8_t* contact0, const float* wrench, float* x_next) {
-  return plant_step_host(h, B, plant, nullptr, x_fb, u0, foot, contact0, wrench, x_next);
+  return plant_step_host(h, B, plant, nullptr, nullptr, x_fb, u0, foot, contact0, wrench, x_next, nullptr, nullptr);
 }
 
 int bmpc_plant_step_body_device(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const float* x_fb,
                                 const float* u0, const float* foot, const uint8_t* contact0, const float* wrench, float* x_next,
                                 void* stream) {
-  return plant_step_device(h, B, plant, body, x_fb, u0, foot, contact0, wrench, x_next, stream);
+  return plant_step_device(h, B, plant, body, nullptr, x_fb, u0, foot, contact0, wrench, x_next, nullptr, nullptr, stream);
 }
 
 int bmpc_plant_step_body(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const float* x_fb,
                          const float* u0, const float* foot, const uint8_t* contact0, const float* wrench, float* x_next) {
-  return plant_step_host(h, B, plant, body, x_fb, u0, foot, contact0, wrench, x_next);
+  return plant_step_host(h, B, plant, body, nullptr, x_fb, u0, foot, contact0, wrench, x_next, nullptr, nullptr);
 }
 
-// bmpc_simulate_device and bmpc_simulate_body_device: closed_loop() with the plant's feedback step.  Without a body and without
-// an outcome that step is simulate_feedback_kernel; else simulate_body_feedback_kernel, after the outcome arrays are initialised
-// on the stream (-1, NaN, NaN; status_any is zeroed by closed_loop the same way).
-static int simulate(bmpc_handle h, int B, int steps, const bmpc_plant* plant, const bmpc_plant_body* body, float* x_fb, float* foot,
-                    double* t, const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push, float* u0_traj,
-                    float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any, const bmpc_sim_outcome* outcome,
-                    void* stream) {
+int bmpc_plant_step_ground_device(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body,
+                                  const bmpc_plant_ground* ground, const float* x_fb, const float* u0, const float* foot,
+                                  const uint8_t* contact0, const float* wrench, float* x_next, float* u_applied, uint8_t* flags,
+                                  void* stream) {
+  return plant_step_device(h, B, plant, body, ground, x_fb, u0, foot, contact0, wrench, x_next, u_applied, flags, stream);
+}
+
+int bmpc_plant_step_ground(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                           const float* x_fb, const float* u0, const float* foot, const uint8_t* contact0, const float* wrench,
+                           float* x_next, float* u_applied, uint8_t* flags) {
+  return plant_step_host(h, B, plant, body, ground, x_fb, u0, foot, contact0, wrench, x_next, u_applied, flags);
+}
+
+// bmpc_simulate_device, bmpc_simulate_body_device and bmpc_simulate_ground_device: closed_loop() with the plant's feedback step.
+// Without a ground, a body and an outcome that step is simulate_feedback_kernel; without a ground simulate_body_feedback_kernel;
+// with one simulate_ground_feedback_kernel, and ground_reduce_kernel in front of it where a reduced array is wanted.  The
+// outcome's and the ground's reduced arrays are initialised on the stream (-1, NaN, NaN; -1, 0, 0, NaN; status_any is zeroed by
+// closed_loop the same way).
+static int simulate(bmpc_handle h, int B, int steps, const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                    float* x_fb, float* foot, double* t, const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push,
+                    float* u0_traj, float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any,
+                    const bmpc_sim_outcome* outcome, const bmpc_ground_out* gout, void* stream) {
   bmpc_plant o;
   if (int rc = plant_opts(plant, &o); rc != BMPC_OK) return rc;
   if (outcome && (outcome->tilt_max != outcome->tilt_max || outcome->z_min != outcome->z_min))
     return fail(BMPC_ERR_INVALID, "outcome thresholds tilt_max and z_min must not be NaN");
+  if (int rc = ground_opts(ground, nullptr, nullptr, gout); rc != BMPC_OK) return rc;
   if (int rc = check_batch(h, B); rc < 0) return rc;
   if (steps < 0) return fail(BMPC_ERR_INVALID, "steps must be >= 0");
   if (B == 0 || steps == 0) return BMPC_OK;
@@ -1288,13 +1330,33 @@ static int simulate(bmpc_handle h, int B, int steps, const bmpc_plant* plant, co
     if (O.max_tilt) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(O.max_tilt), 0x7fc00000, n, st));   // NaN
     if (O.min_z) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(O.min_z), 0x7fc00000, n, st));
   }
+  bmpc::PlantGroundSum R = {0.0, nullptr, nullptr, nullptr, nullptr};
+  if (has_ground_sum(gout)) {
+    R = {gout->fz_floor, gout->first_slip, gout->slip_periods, gout->unloaded_periods, gout->mu_demand};
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = pick_stream(h, stream);
+    if (R.first_slip) HIP_TRY(hipMemsetAsync(R.first_slip, 0xff, n * sizeof(int32_t), st));              // -1
+    if (R.slip_periods) HIP_TRY(hipMemsetAsync(R.slip_periods, 0, n * 2 * sizeof(int32_t), st));
+    if (R.unloaded_periods) HIP_TRY(hipMemsetAsync(R.unloaded_periods, 0, n * 2 * sizeof(int32_t), st));
+    if (R.mu_demand) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(R.mu_demand), 0x7fc00000, n, st));   // NaN
+  }
   return closed_loop(h, B, steps, x_fb, foot, t, gait, x_cmd, mu, status_any, stream, [&](int s, hipStream_t st) {
     const bool push_on = push && s >= o.push_from && s - o.push_from < o.push_steps;
     const float* w = push_on ? push : nullptr;
     float *u0_s = u0_traj ? u0_traj + (size_t)s * n * 12 : nullptr, *x_s = x_traj ? x_traj + (size_t)s * n * 12 : nullptr,
           *foot_s = foot_traj ? foot_traj + (size_t)s * n * 6 : nullptr;
     int32_t* iters_s = iters_traj ? iters_traj + (size_t)s * n : nullptr;
-    if (ext)
+    if (ground) {
+      // (the reduction first: it reads the solve's outputs, which the feedback step leaves alone, and nothing that step writes)
+      if (has_ground_sum(gout))
+        hipLaunchKernelGGL(bmpc::ground_reduce_kernel, dim3((B + 255) / 256), dim3(256), 0, st, ground->mu, h->params.mu, R, s, B,
+                           (int)h->dev.h, h->ro_controls.p, h->ro_contact.p);
+      const bmpc::PlantGround Gr = {ground->mu, h->params.mu, gout && gout->u_applied ? gout->u_applied + (size_t)s * n * 12 : nullptr,
+                                    gout && gout->flags ? gout->flags + (size_t)s * n : nullptr};
+      hipLaunchKernelGGL(bmpc::simulate_ground_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, P, Bd, O, Gr, s, S, PG, B,
+                         h->ro_controls.p, h->ro_contact.p, h->ro_iters.p, h->ro_status.p, w, x_cmd, x_fb, foot, t, u0_s, x_s, foot_s,
+                         iters_s, status_any);
+    } else if (ext)
       hipLaunchKernelGGL(bmpc::simulate_body_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, P, Bd, O, s, S, PG, B,
                          h->ro_controls.p, h->ro_contact.p, h->ro_iters.p, h->ro_status.p, w, x_cmd, x_fb, foot, t, u0_s, x_s, foot_s,
                          iters_s, status_any);
@@ -1308,16 +1370,25 @@ static int simulate(bmpc_handle h, int B, int steps, const bmpc_plant* plant, co
 int bmpc_simulate_device(bmpc_handle h, int B, int steps, const bmpc_plant* plant, float* x_fb, float* foot, double* t,
                          const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push, float* u0_traj,
                          float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any, void* stream) {
-  return simulate(h, B, steps, plant, nullptr, x_fb, foot, t, gait, x_cmd, mu, push, u0_traj, x_traj, foot_traj, iters_traj, status_any,
-                  nullptr, stream);
+  return simulate(h, B, steps, plant, nullptr, nullptr, x_fb, foot, t, gait, x_cmd, mu, push, u0_traj, x_traj, foot_traj, iters_traj,
+                  status_any, nullptr, nullptr, stream);
 }
 
 int bmpc_simulate_body_device(bmpc_handle h, int B, int steps, const bmpc_plant* plant, const bmpc_plant_body* body, float* x_fb,
                               float* foot, double* t, const bmpc_gait* gait, const float* x_cmd, const float* mu, const float* push,
                               float* u0_traj, float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any,
                               const bmpc_sim_outcome* outcome, void* stream) {
-  return simulate(h, B, steps, plant, body, x_fb, foot, t, gait, x_cmd, mu, push, u0_traj, x_traj, foot_traj, iters_traj, status_any,
-                  outcome, stream);
+  return simulate(h, B, steps, plant, body, nullptr, x_fb, foot, t, gait, x_cmd, mu, push, u0_traj, x_traj, foot_traj, iters_traj,
+                  status_any, outcome, nullptr, stream);
+}
+
+int bmpc_simulate_ground_device(bmpc_handle h, int B, int steps, const bmpc_plant* plant, const bmpc_plant_body* body,
+                                const bmpc_plant_ground* ground, float* x_fb, float* foot, double* t, const bmpc_gait* gait,
+                                const float* x_cmd, const float* mu, const float* push, float* u0_traj, float* x_traj,
+                                float* foot_traj, int32_t* iters_traj, int32_t* status_any, const bmpc_sim_outcome* outcome,
+                                const bmpc_ground_out* gout, void* stream) {
+  return simulate(h, B, steps, plant, body, ground, x_fb, foot, t, gait, x_cmd, mu, push, u0_traj, x_traj, foot_traj, iters_traj,
+                  status_any, outcome, gout, stream);
 }
 
 int bmpc_set_dispatch_order(bmpc_handle h, const int32_t* order_dev, int longest_first_rollouts) {

@@ -5,6 +5,9 @@
 //   simulate_feedback_kernel one closed-loop period: integrate x_fb under controls[:, 0], advance t, move landing feet, record
 //   plant_body, plant_outcome, plant_step_body_kernel, simulate_body_feedback_kernel: the same with the rigid body (m, I_b, g) taken
 //                            per instance, and each instance's fall outcome reduced over the periods (at the end of this file's parts)
+//   plant_ground, plant_ground_reduce, plant_step_ground_kernel, simulate_ground_feedback_kernel: the same with a ground under the
+//                            plant -- a friction cone and unilateral contact on what each stance leg transmits, per-leg friction
+//                            per instance, and who slipped reduced over the periods (behind the body's parts)
 // State x = [e(3), p(3), w(3), v(3)], e = [roll, pitch, yaw], w and v in the world frame (REF:13).  Held over the period: the
 // controls u = [f1 f2 m1 m2], the feet r_0, r_1, the contact bits c_0, c_1 and an external wrench [F(3), M(3)] (world frame).
 //   R = Rz(e2) Ry(e1) Rx(e0) (REF:124-138),  I_w = R I_b R'
@@ -246,6 +249,87 @@ __device__ __forceinline__ void plant_outcome(const double tilt_max, const doubl
   min_z = fminf(min_z, x[5]);
 }
 
+// ---- The ground under the plant: what of the commanded controls a flat floor at z = 0 with Coulomb friction transmits.
+
+constexpr int GROUND_SLIP = 1, GROUND_UNLOADED = 4;      // flag bits of leg 0; leg 1: shifted left by one
+
+// One instance, once per control period, before the integration (the controls are held and the ground is flat, so the rule does
+// not depend on the state).  Leg g with contact bit c_g, commanded f = (fx, fy, fz), m and true friction mu_g transmits
+//   c_g == 0:                 nothing (its six values are +0), as plant_held gates it
+//   c_g == 1, not fz > 0:     nothing either -- the ground cannot pull, and passes no moment without load; flag UNLOADED << g
+//   c_g == 1, fz > 0:         fz and m with their bits; fx, fy with their bits while t = sqrt(fx^2 + fy^2) <= lim = mu_g fz, else
+//                             scaled by lim / t in fp64 and rounded to fp32 once each; flag SLIP << g
+// ua: the applied controls in the layout of u.  mu_g may be +inf (no friction limit; it is multiplied for loaded legs only).
+// demand: the largest t / fz over the loaded legs with fz >= fz_floor, as fp32, NaN if there is none.  Returns false, with ua
+// and demand all NaN and no flag, for a bad instance: a mu that is NaN or negative, or a control that is not finite (either leg,
+// whatever its contact bit).  No contraction here: every operation is the correctly rounded one of its line.
+// Not modelled: a slipping foot does not slide (its foothold stays), moments have no limit (centre of pressure, torsion), static
+// and kinetic friction are one number.
+__device__ __forceinline__ bool plant_ground(const float (&u)[12], const bool c0, const bool c1, const double mu0, const double mu1,
+                                             const double fz_floor, float (&ua)[12], uint8_t& flags, float& demand) {
+#pragma clang fp contract(off)
+  const bool c[2] = {c0, c1};
+  const double mu[2] = {mu0, mu1};
+  bool ok = mu0 >= 0.0 && mu1 >= 0.0;            // (false for NaN)
+#pragma unroll
+  for (int i = 0; i < 12; ++i) ok = ok && plant_finite(u[i]);
+  int fl = 0;
+  double dem = __builtin_nan("");
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const float fx = u[3 * g], fy = u[3 * g + 1], fz = u[3 * g + 2];
+    const bool loaded = c[g] && fz > 0.f;
+    if (c[g] && !loaded) fl |= GROUND_UNLOADED << g;
+    float ax = loaded ? fx : 0.f, ay = loaded ? fy : 0.f;
+    if (loaded) {
+      const double dx = (double)fx, dy = (double)fy, dz = (double)fz;
+      const double t = sqrt(dx * dx + dy * dy), lim = mu[g] * dz;
+      if (t > lim) {
+        const double sc = lim / t;
+        ax = (float)(dx * sc); ay = (float)(dy * sc);
+        fl |= GROUND_SLIP << g;
+      }
+      if (dz >= fz_floor) dem = fmax(dem, t / dz);
+    }
+    ua[3 * g] = ax; ua[3 * g + 1] = ay; ua[3 * g + 2] = loaded ? fz : 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ua[6 + 3 * g + i] = loaded ? u[6 + 3 * g + i] : 0.f;
+  }
+  if (!ok) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) ua[i] = __builtin_nanf("");
+    fl = 0; dem = __builtin_nan("");
+  }
+  flags = (uint8_t)fl;
+  demand = (float)dem;
+  return ok;
+}
+
+// A ground step: plant_step_body under what the ground transmits of u, with the same contact bits -- exactly
+// plant_step_body(ua).  A bad ground makes ua, and with it the next state, all NaN.
+__device__ __forceinline__ bool plant_step_ground(const PlantParams& P, const double* m, const double* I9, const double* g,
+                                                  const double mu0, const double mu1, const double fz_floor, const PlantScheme& S,
+                                                  const float (&x)[12], const float (&u)[12], const float (&r)[6], const bool c0,
+                                                  const bool c1, const float (&w)[6], double (&xn)[12], float (&ua)[12],
+                                                  uint8_t& flags, float& demand) {
+  const bool ok = plant_ground(u, c0, c1, mu0, mu1, fz_floor, ua, flags, demand);
+  return plant_step_body(P, m, I9, g, S, x, ua, r, c0 ? 1.0 : 0.0, c1 ? 1.0 : 0.0, w, xn) && ok;
+}
+
+// What the closed loop keeps of the ground per instance, reduced over the periods: the flags and the demand of period s into
+// first_slip (the first s with a slip bit; -1 so far: none), the periods each leg slipped / was unloaded, and the largest demand
+// (fmaxf from a NaN start: periods without a demand are skipped).
+__device__ __forceinline__ void plant_ground_reduce(const uint8_t flags, const float demand, const int s, int32_t& first_slip,
+                                                    int32_t (&slip)[2], int32_t (&unloaded)[2], float& mu_demand) {
+  if ((flags & (GROUND_SLIP | GROUND_SLIP << 1)) && first_slip < 0) first_slip = s;
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    slip[g] += (flags >> g) & 1;
+    unloaded[g] += (flags >> (2 + g)) & 1;
+  }
+  mu_demand = fmaxf(mu_demand, demand);
+}
+
 }  // namespace bmpc
 
 #ifndef BMPC_EMU
@@ -479,6 +563,200 @@ simulate_body_feedback_kernel(const PlantParams P, const PlantBody Bd, const Pla
   if (b >= B) return;
   feedback_body_instance(P, Bd, O, s, S, G, b, controls, contact, iters, status, push, x_cmd, x_fb, foot, t, u0_out, x_out, foot_out,
                           iters_out, status_any);
+}
+
+// The ground as the kernels get it: mu [B][2] per leg (null: mu_h, the handle's, for both legs), and what is recorded of THIS
+// period: u_applied [B][12] and flags [B] (each null: not wanted).
+struct PlantGround {
+  const double* mu;
+  double mu_h;
+  float* u_applied;
+  uint8_t* flags;
+};
+// What the closed loop reduces of the ground over the periods: the floor of the demand, first_slip [B], slip_periods [B][2],
+// unloaded_periods [B][2], mu_demand [B] (each null: not wanted).
+struct PlantGroundSum {
+  double fz_floor;
+  int32_t *first_slip, *slip_periods, *unloaded_periods;
+  float* mu_demand;
+};
+
+// One instance of plant_step_ground_kernel: plant_step_body_instance's with the ground Gr in front of the step.
+__device__ __forceinline__ void plant_step_ground_instance(const PlantParams& P, const PlantBody& Bd, const PlantGround& Gr,
+                                                           const PlantScheme& S, const int b, const float* __restrict__ x_fb,
+                                                           const float* __restrict__ u0, const float* __restrict__ foot,
+                                                           const uint8_t* __restrict__ contact0, const float* __restrict__ wrench,
+                                                           float* __restrict__ x_next) {
+  float x[12], u[12], ua[12], r[6], w[6];
+  double xn[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { x[i] = x_fb[(size_t)b * 12 + i]; u[i] = u0[(size_t)b * 12 + i]; }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { r[i] = foot[(size_t)b * 6 + i]; w[i] = wrench ? wrench[(size_t)b * 6 + i] : 0.f; }
+  const bool c0 = contact0[(size_t)b * 2] != 0, c1 = contact0[(size_t)b * 2 + 1] != 0;
+  const double mu0 = Gr.mu ? Gr.mu[(size_t)b * 2] : Gr.mu_h, mu1 = Gr.mu ? Gr.mu[(size_t)b * 2 + 1] : Gr.mu_h;
+  uint8_t fl;
+  float demand;                                  // (not wanted here: the floor does not matter)
+  plant_ground(u, c0, c1, mu0, mu1, 0.0, ua, fl, demand);
+  // (what does not depend on the step comes first, as in the feedback kernels)
+  if (Gr.u_applied) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) Gr.u_applied[(size_t)b * 12 + i] = ua[i];
+  }
+  if (Gr.flags) Gr.flags[b] = fl;
+  plant_step_body(P, Bd.m ? Bd.m + b : nullptr, Bd.I ? Bd.I + (size_t)b * 9 : nullptr, Bd.g ? Bd.g + b : nullptr, S, x, ua, r,
+                  c0 ? 1.0 : 0.0, c1 ? 1.0 : 0.0, w, xn);
+#pragma unroll
+  for (int i = 0; i < 12; ++i) x_next[(size_t)b * 12 + i] = (float)xn[i];
+}
+
+// One instance of simulate_ground_feedback_kernel: feedback_body_instance's period, statement for statement, with the ground Gr
+// in front of the step -- the plant integrates what the ground transmits of the commanded control, u0_out keeps recording the
+// command.  (Written out a third time for the reason given there: the kernels above are held to their instruction sequences.
+// What is reduced of the ground over the periods is ground_reduce_kernel's: this kernel holds every scalar register it can get
+// where the body is formed, and four more pointers made it spill them.)
+__device__ __forceinline__ void feedback_ground_instance(const PlantParams& P, const PlantBody& Bd, const PlantOutcome& O,
+                                                         const PlantGround& Gr, const int s, const PlantScheme& S, const PlantGait& G,
+                                                         const int b, const float* __restrict__ controls,
+                                                         const uint8_t* __restrict__ contact, const int32_t* __restrict__ iters,
+                                                         const int32_t* __restrict__ status, const float* __restrict__ push,
+                                                         const float* __restrict__ x_cmd, float* __restrict__ x_fb, float* foot,
+                                                         double* __restrict__ t, float* __restrict__ u0_out, float* __restrict__ x_out,
+                                                         float* __restrict__ foot_out, int32_t* __restrict__ iters_out,
+                                                         int32_t* __restrict__ status_any) {
+  const int h = (int)P.h;
+  const float* u0 = controls + (size_t)b * h * 12;
+  float x[12], u[12], ua[12], r[6], w[6];
+  double xn[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { x[i] = x_fb[(size_t)b * 12 + i]; u[i] = u0[i]; }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { r[i] = foot[(size_t)b * 6 + i]; w[i] = push ? push[(size_t)b * 6 + i] : 0.f; }
+  // What does not depend on the step comes first (the commanded and the applied control, the ground's flags, the
+  // iteration count, the solver's status): behind the step, its loads are hoisted above the stages and sit in registers there.
+  if (u0_out) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) u0_out[(size_t)b * 12 + i] = u[i];
+  }
+  if (iters_out) iters_out[b] = iters[b];
+  if (status_any) status_any[b] |= status[b];
+  const uint8_t* row0 = contact + (size_t)b * h * 2;
+  const bool c0 = row0[0] != 0, c1 = row0[1] != 0;
+  const double mu0 = Gr.mu ? Gr.mu[(size_t)b * 2] : Gr.mu_h, mu1 = Gr.mu ? Gr.mu[(size_t)b * 2 + 1] : Gr.mu_h;
+  uint8_t fl;
+  float demand;                                  // (not wanted here: the floor does not matter)
+  plant_ground(u, c0, c1, mu0, mu1, 0.0, ua, fl, demand);
+  if (Gr.u_applied) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) Gr.u_applied[(size_t)b * 12 + i] = ua[i];
+  }
+  if (Gr.flags) Gr.flags[b] = fl;
+  const bool ok = plant_step_body(P, Bd.m ? Bd.m + b : nullptr, Bd.I ? Bd.I + (size_t)b * 9 : nullptr, Bd.g ? Bd.g + b : nullptr, S, x,
+                                  ua, r, c0 ? 1.0 : 0.0, c1 ? 1.0 : 0.0, w, xn);
+  if (!ok && status_any) status_any[b] |= 2;      // BMPC_NUMERICAL
+  float xf[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    xf[i] = (float)xn[i];
+    x_fb[(size_t)b * 12 + i] = xf[i];
+    if (x_out) x_out[(size_t)b * 12 + i] = xf[i];
+  }
+  if (O.first_fall || O.max_tilt || O.min_z) {
+    // (the entry initialised the three arrays on the stream: -1, NaN, NaN)
+    int32_t first = O.first_fall ? O.first_fall[b] : 0;
+    float mt = O.max_tilt ? O.max_tilt[b] : 0.f, mz = O.min_z ? O.min_z[b] : 0.f;
+    plant_outcome(O.tilt_max, O.z_min, xf, s, first, mt, mz);
+    if (O.first_fall) O.first_fall[b] = first;
+    if (O.max_tilt) O.max_tilt[b] = mt;
+    if (O.min_z) O.min_z[b] = mz;
+  }
+  const double t0 = t[b], t1 = t0 + P.dt;
+  t[b] = t1;
+  // the schedule steps of t0 and t1, as gait_kernel finds them (REF:56-57)
+  double ka = fmod(py_floordiv(t0, P.dt), P.h), kb = fmod(py_floordiv(t1, P.dt), P.h);
+  if (ka < 0) ka += P.h;
+  if (kb < 0) kb += P.h;
+  const int k0 = (int)ka, k1 = (int)kb;
+  float rf[6];                                   // (`foot` is not __restrict__: read again here, not carried through the stages)
+#pragma unroll
+  for (int i = 0; i < 6; ++i) rf[i] = foot[(size_t)b * 6 + i];
+  if (G.move_feet) {
+    // the target is taken at the fp32 state the next solve will see
+    double xs[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) xs[i] = xf[i];
+    const double cx = x_cmd ? (double)x_cmd[(size_t)b * 12 + 3] : P.cmd_x, cy = x_cmd ? (double)x_cmd[(size_t)b * 12 + 4] : P.cmd_y;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      double rg[3];
+      if (plant_land(P, k0, k1, G.offset[g], G.period, G.duty[g], g == 0 ? 1.0 : -1.0, xs, cx, cy, rg)) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          rf[3 * g + i] = (float)rg[i];
+          foot[(size_t)b * 6 + 3 * g + i] = rf[3 * g + i];
+        }
+      }
+    }
+  }
+  if (foot_out) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) foot_out[(size_t)b * 6 + i] = rf[i];
+  }
+}
+
+// The two body kernels with the ground under the plant (Gr; plant_ground): the body stays optional (null members of Bd: the
+// handle's) and the fall outcome is still reduced.  Three waves per SIMD like the body kernels: the ground is done before the
+// stages begin and leaves twelve fp32 values where the command was.
+// ground_reduce_kernel: what the closed loop keeps of the ground over the periods (R; plant_ground_reduce), from the same inputs
+// as the feedback kernel of period s -- controls[b, 0, :], row 0 of the contact table, mu -- through the same plant_ground, so
+// that its flags are the recorded ones bit for bit.  It reads nothing the feedback kernel writes.
+__global__ void __launch_bounds__(256, 3)
+plant_step_ground_kernel(const PlantParams P, const PlantBody Bd, const PlantGround Gr, const PlantScheme S, const int B,
+                         const float* __restrict__ x_fb, const float* __restrict__ u0, const float* __restrict__ foot,
+                         const uint8_t* __restrict__ contact0, const float* __restrict__ wrench, float* __restrict__ x_next) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  plant_step_ground_instance(P, Bd, Gr, S, b, x_fb, u0, foot, contact0, wrench, x_next);
+}
+
+__global__ void __launch_bounds__(256, 3)
+simulate_ground_feedback_kernel(const PlantParams P, const PlantBody Bd, const PlantOutcome O, const PlantGround Gr, const int s,
+                                const PlantScheme S, const PlantGait G, const int B, const float* __restrict__ controls,
+                                const uint8_t* __restrict__ contact, const int32_t* __restrict__ iters,
+                                const int32_t* __restrict__ status, const float* __restrict__ push, const float* __restrict__ x_cmd,
+                                float* __restrict__ x_fb, float* foot, double* __restrict__ t, float* __restrict__ u0_out,
+                                float* __restrict__ x_out, float* __restrict__ foot_out, int32_t* __restrict__ iters_out,
+                                int32_t* __restrict__ status_any) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  feedback_ground_instance(P, Bd, O, Gr, s, S, G, b, controls, contact, iters, status, push, x_cmd, x_fb, foot, t, u0_out, x_out,
+                           foot_out, iters_out, status_any);
+}
+
+__global__ void __launch_bounds__(256)
+ground_reduce_kernel(const double* __restrict__ mu, const double mu_h, const PlantGroundSum R, const int s, const int B, const int h,
+                     const float* __restrict__ controls, const uint8_t* __restrict__ contact) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float* u0 = controls + (size_t)b * h * 12;
+  const uint8_t* row0 = contact + (size_t)b * h * 2;
+  float u[12], ua[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) u[i] = u0[i];
+  uint8_t fl;
+  float demand;
+  plant_ground(u, row0[0] != 0, row0[1] != 0, mu ? mu[(size_t)b * 2] : mu_h, mu ? mu[(size_t)b * 2 + 1] : mu_h, R.fz_floor, ua, fl, demand);
+  // (the entry initialised the four arrays on the stream: -1, 0, 0, NaN)
+  int32_t first = R.first_slip ? R.first_slip[b] : 0;
+  int32_t sl[2] = {0, 0}, un[2] = {0, 0};
+  if (R.slip_periods) { sl[0] = R.slip_periods[(size_t)b * 2]; sl[1] = R.slip_periods[(size_t)b * 2 + 1]; }
+  if (R.unloaded_periods) { un[0] = R.unloaded_periods[(size_t)b * 2]; un[1] = R.unloaded_periods[(size_t)b * 2 + 1]; }
+  float dm = R.mu_demand ? R.mu_demand[b] : 0.f;
+  plant_ground_reduce(fl, demand, s, first, sl, un, dm);
+  if (R.first_slip) R.first_slip[b] = first;
+  if (R.slip_periods) { R.slip_periods[(size_t)b * 2] = sl[0]; R.slip_periods[(size_t)b * 2 + 1] = sl[1]; }
+  if (R.unloaded_periods) { R.unloaded_periods[(size_t)b * 2] = un[0]; R.unloaded_periods[(size_t)b * 2 + 1] = un[1]; }
+  if (R.mu_demand) R.mu_demand[b] = dm;
 }
 
 }  // namespace bmpc

@@ -647,6 +647,61 @@ int bmpc_simulate_body_device(bmpc_handle h, int B, int steps, const bmpc_plant*
                               float* u0_traj, float* x_traj, float* foot_traj, int32_t* iters_traj, int32_t* status_any,
                               const bmpc_sim_outcome* outcome, void* stream);
 
+/*
+ * A ground under the plant: friction cone, unilateral contact, and who slipped (added under ABI 13 like the entries above: detect
+ * them by the symbol).  The entries above pass on whatever the controller asks for: a stance leg can pull on the ground and push
+ * sideways with any force.  These put a flat floor with Coulomb friction between the controller and the body.  The rule is applied
+ * per instance once per control period, before the integration, in fp64 on the fp32 controls (they are held over the period and the
+ * ground is flat, so it does not depend on the state).  For leg g with contact bit c_g, commanded f = (fx, fy, fz), m and true
+ * friction mu_g:
+ *   c_g == 0                 the leg transmits nothing, as above: its 6 applied values are +0
+ *   c_g == 1, not fz > 0     UNLOADED: the ground cannot pull and passes no moment without load; all 6 are +0; flag bit 4 << g
+ *   c_g == 1, fz > 0         LOADED: with t = sqrt(fx fx + fy fy) and lim = mu_g fz, the leg SLIPS if t > lim: fx and fy are scaled
+ *                            by lim / t in fp64, each rounded to fp32 once, flag bit 1 << g; otherwise fx and fy pass with their bits
+ *                            (t == lim holds).  fz and m always pass with their bits.
+ * mu_g may be +inf (no friction limit; it is multiplied for loaded legs only).  A mu_g that is NaN or negative, or a control that
+ * is not finite (either leg, whatever its contact bit), is a bad instance: u_applied all NaN, flags 0, the next state all NaN,
+ * BMPC_NUMERICAL in status_any, like a bad body; no other instance is touched.  The DEMAND of a period is the largest t / fz over the
+ * loaded legs with fz >= fz_floor, NaN if there is none.  The plant integrates the applied controls as stored in fp32 with the same
+ * contact bits: a ground step is exactly the body step at u_applied.
+ * Limits: a slipping foot does not slide (its foothold stays); moments have no limit (no centre of pressure, no torsional
+ * friction); static and kinetic friction are one number; the ground is flat at z = 0.
+ *   bmpc_plant_ground   mu [B][2] per leg, fp64; NULL: the handle's params.mu for both legs -- the true cone against the
+ *                       controller's pyramid.  The solve inside the loop keeps reading the handle's block and the caller's
+ *                       mu [B][h][2], the controller's BELIEF, exactly as before.
+ *   bmpc_ground_out     what the closed loop records of the ground; each pointer may be NULL.  The reduced arrays (first_slip,
+ *                       slip_periods, unloaded_periods, mu_demand) are initialised by the entry on the stream (-1, 0, 0, NaN).
+ *                       fz_floor NaN or negative is BMPC_ERR_INVALID (checked with the plant block, before the handle).
+ *   bmpc_plant_step_ground_device / bmpc_plant_step_ground   bmpc_plant_step_body_device / bmpc_plant_step_body with `ground`
+ *                       (DEVICE / HOST pointers, members and u_applied, flags included)
+ *   bmpc_simulate_ground_device   bmpc_simulate_body_device with `ground` and `gout` (DEVICE pointers); u0_traj keeps recording the
+ *                       controller's command
+ * `ground` NULL runs the body entries, bit for bit; a non-NULL u_applied, flags or gout is then BMPC_ERR_INVALID (checked before
+ * the handle).  `body` stays optional and `outcome` is reduced as before.
+ */
+typedef struct bmpc_plant_ground { const double* mu; } bmpc_plant_ground;   /* [B][2] per leg, fp64; NULL -> params.mu for both legs */
+typedef struct bmpc_ground_out {
+  double fz_floor;            /* mu_demand counts a leg only while fz >= fz_floor; >= 0; NaN or negative: BMPC_ERR_INVALID */
+  float* u_applied;           /* [steps][B][12] what reached the body each period */
+  uint8_t* flags;             /* [steps][B]: 1, 2 leg 0 / 1 slipped; 4, 8 leg 0 / 1 unloaded */
+  int32_t* first_slip;        /* [B] first period with a slip bit, or -1 */
+  int32_t* slip_periods;      /* [B][2] periods each leg slipped */
+  int32_t* unloaded_periods;  /* [B][2] */
+  float* mu_demand;           /* [B] max over the periods (fp32, NaN periods skipped), NaN if none */
+} bmpc_ground_out;            /* each pointer may be NULL; the entry initialises the reduced arrays on the stream */
+int bmpc_plant_step_ground_device(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body,
+                                  const bmpc_plant_ground* ground, const float* x_fb, const float* u0, const float* foot,
+                                  const uint8_t* contact0, const float* wrench, float* x_next, float* u_applied /* [B][12] or NULL */,
+                                  uint8_t* flags /* [B] or NULL */, void* stream);
+int bmpc_plant_step_ground(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body,
+                           const bmpc_plant_ground* ground, const float* x_fb, const float* u0, const float* foot,
+                           const uint8_t* contact0, const float* wrench, float* x_next, float* u_applied, uint8_t* flags);
+int bmpc_simulate_ground_device(bmpc_handle h, int B, int steps, const bmpc_plant* plant, const bmpc_plant_body* body,
+                                const bmpc_plant_ground* ground, float* x_fb, float* foot, double* t, const bmpc_gait* gait,
+                                const float* x_cmd, const float* mu, const float* push, float* u0_traj, float* x_traj,
+                                float* foot_traj, int32_t* iters_traj, int32_t* status_any, const bmpc_sim_outcome* outcome,
+                                const bmpc_ground_out* gout, void* stream);
+
 /* Diagnostics: when device_buf (DEVICE pointer, [max_batch][16] int64) is non-NULL every later solve
  * writes per-instance shader-clock stamps {setup, block algebra, dense sweeps, total, iters,
  * factorisations, -, -, iteration phases P0..P5, stop test + adaptation, -}; NULL switches it off
