@@ -61,11 +61,14 @@ enum bmpc_rescue_mode {
 /* per-instance status[] values written by the solver */
 enum bmpc_instance_status {
   BMPC_SOLVED = 0,           /* stopping criteria met */
-  BMPC_MAX_ITER = 1,         /* iteration cap reached (result is the last iterate).  The stopping criteria are three: the
-                                primal and the step residual within eps_pri / eps_dua, and no inactive row still pulling
-                                (penalty x |z~ - z| <= 1e-5 x 2 min R x max(1, |x|)); an instance that fails only the third
-                                re-classifies at once, and one that can no longer re-classify (max_refactor spent, or
-                                adapt_every = 0) is accepted on the first two alone -- it is never held to the cap by it */
+  BMPC_MAX_ITER = 1,         /* iteration cap reached (result is the last iterate: iters = max_iter, and iteration max_iter
+                                always ends on a stopping test, so residuals[] are its own and the states those of the returned
+                                controls).  The stopping criteria are four: (1, 2) the primal and the step residual within
+                                eps_pri / eps_dua, (3) no inactive row still pulling (penalty x |z~ - z| <= 1e-6 x 2 min R x
+                                max(1, |x|)), (4) the rows of step 0 -- the applied control -- within 5 x max(eps_pri, eps_dua)
+                                relative to step 0's own norm (not on the dense kernel of h = 12); an instance that fails only
+                                the third re-classifies at once, and one that can no longer re-classify (max_refactor spent, or
+                                adapt_every = 0) is accepted without it -- it is never held to the cap by it */
   BMPC_NUMERICAL = 2         /* NaN/Inf encountered */
 };
 

@@ -306,8 +306,24 @@ def solve_batch(P, x_fb, foot, contact, phase, x_cmd=None, mu=None, dtype=np.flo
     aa_prev_fac = None                            # n_factor when g' was taken
     it_done = np.full(B, n_it)
     active = np.ones(B, bool)
-    for it in range(n_it):
+    # The kernels' test schedule (P.kernel_schedule, off by default: the model then tests every check_every iterations from the
+    # start).  Per instance, as in bmpc_kernels.hip / bmpc_stage.hip: a cold start skips its first test (next_check = 2 check_every),
+    # a test that finds a residual more than FAR times its tolerance away skips the next one, iteration max_iter is always a test,
+    # and there is no secant step on it.  g' is the state change of the iteration BEFORE a test (it + 2 == next_check).
+    ks = bool(getattr(P, "kernel_schedule", False))
+    ce = max(int(P.check_every), 1)
+    next_check = np.full(B, 2 * ce)
+    FAR = 1.0e3
+    aa_have = np.zeros(B, bool)
+    want_res = bool(getattr(P, "want_residuals", False))      # (tests: info["residuals"], those of an instance's last iteration)
+    res_last = np.zeros((B, 2))
+    n_used = n_factor.copy()                      # factorisations an iterate has used (the kernels' nfactor: the last iteration may
+    for it in range(n_it):                        #  prepare one more that nothing uses)
         n_factor_at_step = n_factor.copy()
+        n_used = np.where(active, n_factor, n_used)
+        chk = active & ((it + 1 == next_check) | (it + 1 == P.max_iter)) if ks else np.ones(B, bool)
+        done_now = np.zeros(B, bool)
+        keep_m = (it + 2 == next_check) if ks else None
         rvr = rv.astype(rdt)
         # residual (rdt), formed as ONE control-space vector so that it is small at convergence:
         #   r = W'(Gt W x + qt) + 2R x + A'(y + rho (A x - z))
@@ -331,12 +347,18 @@ def solve_batch(P, x_fb, foot, contact, phase, x_cmd=None, mu=None, dtype=np.flo
         zr = alpha * zt + (1 - alpha) * z
         zn = np.clip(zr + y / rvr, lr, ur)
         yn = y + rvr * (zr - zn)
-        if (it + 1) % P.check_every == 0:
+        # (what a stopping test at this iteration reports -- the kernels' residuals[] when this is the last iteration)
+        if want_res:
+            res_last = np.where(active[:, None], np.stack([np.abs(zt - zn).reshape(B, -1).max(1), np.abs(xt - x).reshape(B, -1).max(1)], 1), res_last)
+        if chk.any() if ks else (it + 1) % P.check_every == 0:
             rp = np.abs(zt - zn).reshape(B, -1).max(1)
             rs = np.abs(xt - x).reshape(B, -1).max(1)                     # preconditioned residual K^-1 r
             sc_p = np.maximum(np.abs(zt).reshape(B, -1).max(1), 1)
             sc_d = np.maximum(np.abs(xt).reshape(B, -1).max(1), 1)
-            done = (rp <= P.eps_pri * sc_p) & (rs <= P.eps_dua * sc_d)
+            done = (rp <= P.eps_pri * sc_p) & (rs <= P.eps_dua * sc_d) & chk
+            if ks:
+                far = (rp > FAR * P.eps_pri * sc_p) | (rs > FAR * P.eps_dua * sc_d)
+                next_check = np.where(chk, next_check + np.where(far, 2 * ce, ce), next_check)
             guard = getattr(P, "slow_guard", 0.0)
             if guard:
                 # An inactive row whose penalty is still far above the floor follows at 1 - alpha c / rho per iteration, c the
@@ -358,55 +380,74 @@ def solve_batch(P, x_fb, foot, contact, phase, x_cmd=None, mu=None, dtype=np.flo
                         L, Na, V = fac(rv)
                         n_factor += ch
             newly = active & done
+            done_now = done
             it_done[newly] = it + 1
             if iters is None:
                 active &= ~done
         keep = active[:, None, None, None]
         aa_g = None
-        if accel and ((it + 2) % P.check_every == 0 or (it + 1) % P.check_every == 0):
+        if accel and ((keep_m.any() or chk.any()) if ks else ((it + 2) % P.check_every == 0 or (it + 1) % P.check_every == 0)):
             aa_g = np.concatenate([(xn - x).reshape(B, -1), (zn - z).reshape(B, -1), (yn - y).reshape(B, -1)], 1).astype(np.float32)
         x = np.where(keep, xn, x)
         z = np.where(keep, zn, z)
         y = np.where(keep, yn, y)
         if not active.any():
             break
+        ks_now = None
+        if ks and accel and aa_g is not None:
+            # (kernels: no step on iteration max_iter, none by an instance that stops, none across a factorisation, none after
+            #  AA_MAX_FACTOR factorisations -- 16 on the long horizons of the stage family, which re-classify twice as often)
+            amax = 16 if (aa_x_only and P.h > 20 and P.adapt_every <= 10) else 8
+            ks_now = chk & active & ~done_now & aa_have & ((it + 1) < P.max_iter) & (aa_prev_fac == n_factor_at_step) & (n_factor_at_step <= amax)
+        z_seen, y_seen = z, y
+        if ks_now is not None and aa_x_only and ks_now.any():
+            # the stage family commits the update of a test's iteration along the secant BEFORE it re-classifies: the new penalties
+            # come from the extrapolated state; whether any penalty moves was decided on the state before it (z_seen, y_seen)
+            x, z, y = _secant_step(aa_g, aa_prev, ks_now, x, z, y, lr, ur, True, rdt)
+            ks_now = None
+        nf_pre = n_factor.copy()
         due = active & ((it + 1) == next_adapt) if P.adapt_every else np.zeros(B, bool)
         if due.any():
             # per-instance schedule (the kernels: every workgroup has its own counters).  Two rates: the first adapt_early
             # re-classifications adapt_every apart, the later ones adapt_late (bmpc_params.adapt_early / adapt_late)
             n_adapt = n_adapt + due
             act = ((z <= lr) | (z >= ur)) & (y != 0)
-            flips = np.where(seen_act, (act != act_prev).reshape(B, -1).sum(1), 0)       # rows whose class changed since the instance's last re-classification
+            act_seen = act if z_seen is z else ((z_seen <= lr) | (z_seen >= ur)) & (y_seen != 0)
+            flips = np.where(seen_act, (act_seen != act_prev).reshape(B, -1).sum(1), 0)  # rows whose class changed since the instance's last re-classification
             late = (getattr(P, "adapt_late", 0) > 0) & (n_adapt >= getattr(P, "adapt_early", 0))
             # (... but adapt_busy after a re-classification that still found more than adapt_flips rows in another class)
             busy = (flips > getattr(P, "adapt_flips", 0)) & (getattr(P, "adapt_busy", 0) > 0)
             period = np.where(late, np.where(busy, getattr(P, "adapt_busy", 0), getattr(P, "adapt_late", 0)), P.adapt_every)
             if P.kappa:
                 # damping as in the kernel: sqrt(kappa) after 10 factorisations, its square root after 16
-                kap = np.where(n_factor <= 10, P.kappa, np.where(n_factor <= 16, P.kappa ** 0.5, P.kappa ** 0.25)).astype(dtp)[:, None, None, None]
-                kc = getattr(P, "kappa_confirm", 0)
-                if kc:
-                    # a row found in the same class as at the instance's previous re-classification is taken at its word: it
-                    # moves by kappa_confirm (>= the distance to its limit: straight there) instead of walking its ladder
-                    conf = (act == act_prev) & (seen_act & (n_adapt > getattr(P, "confirm_from", 0)))[:, None, None, None] & (n_factor <= 10)[:, None, None, None]
-                    kap = np.where(conf, dt_(kc), kap)
-                rvc = np.clip(rv, dt_(P.rho_lo), hi)
-                up = np.minimum(rvc * kap, hi)
-                dn = np.maximum(rvc / kap, dt_(P.rho_lo))
-                rnew = np.where(eq, rho_eq, np.where(act, up, dn)).astype(dtp)
+                def ladder(act_):
+                    kap = np.where(n_factor <= 10, P.kappa, np.where(n_factor <= 16, P.kappa ** 0.5, P.kappa ** 0.25)).astype(dtp)[:, None, None, None]
+                    kc = getattr(P, "kappa_confirm", 0)
+                    if kc:
+                        # a row found in the same class as at the instance's previous re-classification is taken at its word: it
+                        # moves by kappa_confirm (>= the distance to its limit: straight there) instead of walking its ladder
+                        conf = (act_ == act_prev) & (seen_act & (n_adapt > getattr(P, "confirm_from", 0)))[:, None, None, None] & (n_factor <= 10)[:, None, None, None]
+                        kap = np.where(conf, dt_(kc), kap)
+                    rvc = np.clip(rv, dt_(P.rho_lo), hi)
+                    up = np.minimum(rvc * kap, hi)
+                    dn = np.maximum(rvc / kap, dt_(P.rho_lo))
+                    return np.where(eq, rho_eq, np.where(act_, up, dn)).astype(dtp)
+                rnew = ladder(act)
                 rhook = getattr(P, "rnew_hook", None)          # (experiments: any rule; gets the state it may look at)
                 if rhook is not None:
                     rnew = rhook(P, dict(it=it + 1, n_factor=n_factor, rv=rv, rnew=rnew, act=act, eq=eq, hi=hi, z=z, y=y, l=lr, u=ur,
                                          rho_eq=rho_eq, x=x, due=due, flips=flips)).astype(dtp)
+                moves = rnew != rv if act_seen is act else ladder(act_seen) != rv
             else:
                 rnew = np.where(eq, rho_eq, np.where(act, hi, dt_(P.rho_lo))).astype(dtp)
+                moves = rnew != rv
             phook = getattr(P, "period_hook", None)            # (experiments: the next period from what this re-classification saw)
             if phook is not None:
                 period = phook(P, dict(it=it + 1, n_adapt=n_adapt, flips=flips, moved=(rnew != rv).reshape(B, -1).sum(1), period=period, n_factor=n_factor))
             next_adapt = np.where(due, next_adapt + period, next_adapt)
             act_prev = np.where(due[:, None, None, None], act, act_prev)
             seen_act = seen_act | due
-            changed = due & (rnew != rv).reshape(B, -1).any(1) & (n_factor <= P.max_refactor)
+            changed = due & moves.reshape(B, -1).any(1) & (n_factor <= P.max_refactor)
             if changed.any():
                 if getattr(P, "trace", None) is not None:           # (tools: how many steps a re-factorisation really touches)
                     nst = (rnew != rv).any(axis=(2, 3)).sum(1)
@@ -415,7 +456,19 @@ def solve_batch(P, x_fb, foot, contact, phase, x_cmd=None, mu=None, dtype=np.flo
                 L, Na, V = fac(rv)                                   # model: refactor all
                 n_factor += changed
         # (end of the iteration) secant step at a stopping test for the instances that go on
-        if accel and aa_g is not None:
+        if ks:
+            if accel:
+                if ks_now is not None and ks_now.any():
+                    x, z, y = _secant_step(aa_g, aa_prev, ks_now, x, z, y, lr, ur, aa_x_only, rdt)
+                if aa_g is not None and keep_m.any():
+                    aa_prev = aa_g if aa_prev is None else np.where(keep_m[:, None], aa_g, aa_prev)
+                    aa_prev_fac = np.where(keep_m, n_factor_at_step, -1 if aa_prev_fac is None else aa_prev_fac)
+                # g' is dropped by the test it was kept for; on the dense family by any re-classification in between as well
+                # (its reduction shares the test's exchange, and the flag is cleared with it)
+                aa_have = (aa_have | keep_m) & ~chk
+                if not aa_x_only:
+                    aa_have &= ~(due & (nf_pre <= P.max_refactor))
+        elif accel and aa_g is not None:
             if (it + 1) % P.check_every == 0:
                 if aa_prev is not None and (it + 1) < P.max_iter:
                     d = aa_g - aa_prev
@@ -437,11 +490,29 @@ def solve_batch(P, x_fb, foot, contact, phase, x_cmd=None, mu=None, dtype=np.flo
     ctrl = np.concatenate([x[:, :, 0, 0:3], x[:, :, 1, 0:3], x[:, :, 0, 3:6], x[:, :, 1, 3:6]], -1)
     wr = np.einsum("bhfij,bhfj->bhi", Wr, x).astype(dtp)                  # wrench per step
     states = rollout(P, x_fb, Iw_inv, Rinv, wr, dt_)
-    info = dict(iters=it_done, n_factor=n_factor)
+    info = dict(iters=it_done, n_factor=n_factor, n_factor_used=n_used, residuals=res_last)
     if return_debug:
         info.update(x_ref=x_ref, foot_ref=foot_ref, Gt=Gt, qt=qt, s=s, V=V, Iw_inv=Iw_inv, Rinv=Rinv, r=r,
                     rv=rv, x=x, z=z, y=y, l=l, u=u, A=A)
     return states, ctrl, info
+
+
+def _secant_step(aa_g, aa_prev, ok, x, z, y, lr, ur, x_only, rdt):
+    """w <- T(w) - gamma g for the instances `ok`, gamma = <g - g', g> / |g - g'|^2 over the whole state (x_only: over its x part)."""
+    B = x.shape[0]
+    d = aa_g - aa_prev
+    nx_ = x.size // B if x_only else d.shape[1]
+    s1 = np.einsum("bn,bn->b", d[:, :nx_], aa_g[:, :nx_])
+    s2 = np.einsum("bn,bn->b", d[:, :nx_], d[:, :nx_])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gam = s1 / s2
+    okg = ok & (s2 > 0) & (np.abs(gam) < 100.0)
+    gam = np.where(okg, gam, 0.0).astype(rdt)
+    n1, n2 = x.size // B, z.size // B
+    x = x - gam[:, None, None, None] * aa_g[:, :n1].reshape(x.shape).astype(rdt)
+    z = np.clip(z - gam[:, None, None, None] * aa_g[:, n1:n1 + n2].reshape(z.shape).astype(rdt), lr, ur)
+    y = y - gam[:, None, None, None] * aa_g[:, n1 + n2:].reshape(y.shape).astype(rdt)
+    return x, z, y
 
 
 def rollout(P, x_fb, Iw_inv, Rinv, wr, dt_):

@@ -228,27 +228,77 @@ def test_absolute_round_trip_resolves_to_the_same_block(what):
         assert list(lib5) == eff, (what, path, h)
 
 
+def _set(field, value, index=None):
+    def mod(cp):
+        if index is None:
+            setattr(cp, field, value)
+        else:
+            getattr(cp, field)[index] = value
+    return mod
+
+
+def _zero_Q(cp):
+    for i in range(13):
+        cp.Q[i] = 0.0
+
+
+def _singular(cp):
+    for i in range(9):
+        cp.I[i] = 0.0
+
+
+# every refusal branch of `make_dev_params` (biped_mpc_py_amd/csrc/bmpc_host_params.hpp), in its order: (name, change of the default block, a word of
+# the message).  NaN counts as refused wherever the check is written as !(x > 0).
+_REFUSED = [
+    ("horizon", _set("h", 41), "unsupported horizon"), ("horizon_dense", lambda cp: (_set("h", 22)(cp), _set("path", 1)(cp)), "unsupported horizon"),
+    ("path", _set("path", 3), "unsupported horizon"),
+    ("half", _set("half", 0), "half"),
+    ("dt", _set("dt", 0.0), "dt and m"), ("dt_nan", _set("dt", float("nan")), "dt and m"), ("m", _set("m", -1.0), "dt and m"),
+    ("rho", _set("rho", 0.0), "penalties"), ("rho_lo", _set("rho_lo", -1e-4), "penalties"), ("rho_hi_f", _set("rho_hi_f", 0.0), "penalties"),
+    ("rho_hi_m", _set("rho_hi_m", float("nan")), "penalties"), ("rho_eq_scale", _set("rho_eq_scale", 0.0), "penalties"),
+    ("kappa", _set("kappa", 1.0), "kappa must"),
+    ("kappa_confirm", _set("kappa_confirm", 0.5), "kappa_confirm"), ("kappa_confirm_1", _set("kappa_confirm", 1.0), "kappa_confirm"),
+    ("adapt_early", _set("adapt_early", -1), "adapt_early"), ("adapt_late", _set("adapt_late", -1), "adapt_early"),
+    ("adapt_busy", _set("adapt_busy", -2), "adapt_early"), ("adapt_flips", _set("adapt_flips", -1), "adapt_early"),
+    ("confirm_from", _set("confirm_from", -1), "adapt_early"),
+    ("max_iter", _set("max_iter", 0), "max_iter"), ("check_every", _set("check_every", 0), "max_iter"),
+    ("rescue", _set("rescue", 3), "rescue"), ("rescue_low", _set("rescue", -2), "rescue"),
+    ("R_zero", _set("R", 0.0, 7), "R > 0"), ("Q_negative", _set("Q", -1.0, 4), "R > 0"),
+    ("singular", _singular, "singular"),
+    ("f_bounds", _set("f_min", 501.0, 2), "upper bound"), ("tau_bounds", _set("tau_max", -68.0, 1), "upper bound"),
+    ("curvature", _zero_Q, "curvature"),
+    ("penalty_mode", _set("penalty_mode", 2), "penalty_mode"),
+]
+
+
 def test_refused_blocks_are_refused_alike():
-    """A block `make_dev_params` refuses is refused by the library and by the emulation with the same message."""
+    """A block `make_dev_params` refuses is refused by the library and by the emulation with the same message -- every branch:
+    horizon / path, half, dt / m, each penalty, kappa, kappa_confirm, a negative adapt_* field, max_iter / check_every < 1, the
+    rescue mode, R <= 0, Q < 0, a singular inertia, bound order, degenerate curvature under SCALED, an unknown penalty_mode.  The
+    unchanged block is accepted by both, and so is the degenerate-curvature block under ABSOLUTE, as the message advises."""
     import ctypes as C
     import biped_mpc_py_amd as bm
     import __graft_entry__ as ge
     ge.build()
     from biped_mpc_py_amd import _lib
     from tests.emu import emu
-
-    def singular(cp):
-        for i in range(9):
-            cp.I[i] = 0.0
-    for mod, word in ((lambda cp: setattr(cp, "rescue", 3), "rescue"), (singular, "singular"), (lambda cp: setattr(cp, "kappa", 1.0), "kappa")):
+    lib = _lib.load()
+    five = lambda: (C.c_double * 5)()
+    cp = bm.pack_params(bm.MPC(), bm.Biped())
+    assert lib.bmpc_effective_penalties(C.byref(cp), five()) == 0 and emu.dev_params(cp)
+    assert len({r[0] for r in _REFUSED}) == len(_REFUSED) >= 30
+    for what, mod, word in _REFUSED:
         cp = bm.pack_params(bm.MPC(), bm.Biped())
         mod(cp)
-        assert _lib.load().bmpc_effective_penalties(C.byref(cp), (C.c_double * 5)()) == -1
-        msg = _lib.load().bmpc_last_error().decode()
-        assert word in msg
+        assert lib.bmpc_effective_penalties(C.byref(cp), five()) == -1, what
+        msg = lib.bmpc_last_error().decode()
+        assert word in msg, (what, msg)
         with pytest.raises(RuntimeError) as e:
             emu.dev_params(cp)
-        assert str(e.value) == msg
+        assert str(e.value) == msg, what
+        if what == "curvature":
+            cp.penalty_mode = 1                      # BMPC_PENALTY_ABSOLUTE
+            assert lib.bmpc_effective_penalties(C.byref(cp), five()) == 0 and emu.dev_params(cp)
 
 
 def test_kernel_source_hash_covers_code_not_commentary():
