@@ -9,7 +9,7 @@ from .api import (BatchSolver, solve_mpc, solve_mpc_batch, get_contact_sequence,
                   phase_index, phase_indices, lowLevelControl, getFootPositionWorld, SolverStatusWarning,
                   close_cached_solvers, get_reference_trajectory, get_reference_foot_trajectory,
                   reference_trajectories_batch, references_to_kernel_layout, evaluate_mpc, evaluate_mpc_batch,
-                  evaluate_grad_mpc, evaluate_grad_mpc_batch, certify_mpc, certify_mpc_batch, duals_to_reference_order)
+                  evaluate_grad_mpc, evaluate_grad_mpc_batch, evaluate_samples_mpc_batch, certify_mpc, certify_mpc_batch, duals_to_reference_order)
 from . import sharding                                                        # noqa: F401
 from ._lib import BmpcError                                                   # noqa: F401
 
@@ -18,4 +18,4 @@ __all__ = ["MPC", "Biped", "pack_params", "BatchSolver", "solve_mpc", "solve_mpc
            "BmpcError", "SolverStatusWarning", "close_cached_solvers",
            "get_reference_trajectory", "get_reference_foot_trajectory", "reference_trajectories_batch",
            "references_to_kernel_layout", "evaluate_mpc", "evaluate_mpc_batch",
-           "evaluate_grad_mpc", "evaluate_grad_mpc_batch", "certify_mpc", "certify_mpc_batch", "duals_to_reference_order"]
+           "evaluate_grad_mpc", "evaluate_grad_mpc_batch", "evaluate_samples_mpc_batch", "certify_mpc", "certify_mpc_batch", "duals_to_reference_order"]

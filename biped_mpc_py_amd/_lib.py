@@ -21,7 +21,7 @@ EXPORTS = (
     "bmpc_debug_assemble", "bmpc_debug_set_profile", "bmpc_last_kernel_ms",
     "bmpc_solve_inputs_f64", "bmpc_solve_inputs_device", "bmpc_debug_assemble_inputs",
     "bmpc_evaluate_device", "bmpc_evaluate", "bmpc_evaluate_grad_device", "bmpc_evaluate_grad",
-    "bmpc_certify_device", "bmpc_certify",
+    "bmpc_certify_device", "bmpc_certify", "bmpc_evaluate_samples_device", "bmpc_evaluate_samples",
     "bmpc_foot_position_world", "bmpc_foot_position_world_device",
     "bmpc_low_level_control", "bmpc_low_level_control_device",
     "bmpc_gait_default", "bmpc_contact_sequence", "bmpc_contact_sequence_device",
@@ -91,6 +91,16 @@ class CGradOut(C.Structure):
 class CCertOut(C.Structure):
     """`bmpc_cert_out` of include/bmpc.h: the outputs of a KKT certificate, each optional (NULL: not wanted)."""
     _fields_ = [(n, C.c_void_p) for n in ("lam", "resid", "summary", "n_active", "status")]
+
+
+class CSamples(C.Structure):
+    """`bmpc_samples` of include/bmpc.h: samples per instance, the prices of the four violation classes, the temperature."""
+    _fields_ = [("S", C.c_int32), ("reserved0", C.c_int32), ("w_viol", C.c_double * 4), ("temperature", C.c_double)]
+
+
+class CSamplesOut(C.Structure):
+    """`bmpc_samples_out` of include/bmpc.h: per-sample values and per-instance reductions, each optional (NULL: not wanted)."""
+    _fields_ = [(n, C.c_void_p) for n in ("cost", "violation", "score", "best", "n_valid", "weights", "u_mean", "ess")]
 
 
 class BmpcError(RuntimeError):
@@ -188,6 +198,8 @@ def load():
     lib.bmpc_evaluate_grad.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CGradOut)]
     lib.bmpc_certify_device.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.c_double, C.POINTER(CCertOut), vp]
     lib.bmpc_certify.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.c_double, C.POINTER(CCertOut)]
+    lib.bmpc_evaluate_samples_device.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CSamples), C.POINTER(CSamplesOut), vp]
+    lib.bmpc_evaluate_samples.argtypes = [vp, ip, C.POINTER(CInputs), vp, C.POINTER(CSamples), C.POINTER(CSamplesOut)]
     lib.bmpc_foot_position_world.argtypes = [vp, ip, vp, vp, vp]
     lib.bmpc_foot_position_world_device.argtypes = [vp, ip, vp, vp, vp, vp]
     lib.bmpc_low_level_control.argtypes = [vp, ip] + [vp] * 8

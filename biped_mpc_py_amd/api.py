@@ -139,7 +139,8 @@ def duals_to_reference_order(lam):
 
 # The evaluation family (`bmpc_evaluate`, `bmpc_evaluate_grad`, `bmpc_certify` and their _device twins): per operation the ctypes
 # output descriptor, the host and the device entry, whether the entries take `act_tol`, and the outputs in the order of the result
-# dict: (name, dtype, shape in terms of "B" and "h").  `BatchSolver._eval_host` / `_eval_device` do the work for every row.
+# dict: (name, dtype, shape in terms of "B", "h" and -- evaluate_samples -- "S").  `BatchSolver._eval_host` / `_eval_device` do the
+# work for the rows with one plan per instance, `_samples_host` / `evaluate_samples_device` for the row with S of them.
 _EVAL_OPS = {
     "evaluate": (_lib.CEvalOut, "bmpc_evaluate", "bmpc_evaluate_device", False,
                  (("cost", "float64", ("B",)), ("objective", "float64", ("B",)), ("violation", "float64", ("B", 4)),
@@ -149,11 +150,39 @@ _EVAL_OPS = {
     "certify": (_lib.CCertOut, "bmpc_certify", "bmpc_certify_device", True,
                 (("lam", "float64", ("B", "h", 36)), ("resid", "float64", ("B", "h", 12)), ("summary", "float64", ("B", 4)),
                  ("n_active", "int32", ("B",)), ("status", "int32", ("B",)))),
+    "evaluate_samples": (_lib.CSamplesOut, "bmpc_evaluate_samples", "bmpc_evaluate_samples_device", False,
+                         (("cost", "float64", ("B", "S")), ("violation", "float64", ("B", "S", 4)), ("score", "float64", ("B", "S")),
+                          ("best", "int32", ("B",)), ("n_valid", "int32", ("B",)), ("weights", "float64", ("B", "S")),
+                          ("u_mean", "float64", ("B", "h", 12)), ("ess", "float64", ("B",)))),
 }
 
+SAMPLES_MAX = 65536     # samples per instance `evaluate_samples` takes (include/bmpc.h)
 
-def _shape(spec, B, h):
-    return tuple({"B": B, "h": h}.get(d, d) for d in spec)
+
+def _shape(spec, B, h, S=None):
+    return tuple({"B": B, "h": h, "S": S}.get(d, d) for d in spec)
+
+
+def _samples_f32(controls, h, B=None):
+    """Candidate plans as `evaluate_samples` takes them: (B,S,h,12) of any float dtype -> C-contiguous fp32.  Shape checked here
+    (ValueError), before any call."""
+    c = np.asarray(controls)
+    if c.ndim != 4 or c.shape[2:] != (h, 12) or (B is not None and c.shape[0] != B) or not np.issubdtype(c.dtype, np.floating) \
+            or not 1 <= c.shape[1] <= SAMPLES_MAX:
+        raise ValueError(f"controls must be a float array of shape ({'B' if B is None else B}, S, {h}, 12) with 1 <= S <= {SAMPLES_MAX} "
+                         f"(plan s of instance b, row k = [f1 f2 m1 m2]), got {c.dtype} {c.shape}")
+    return np.ascontiguousarray(c, np.float32)
+
+
+def _samples_desc(S, w_viol, temperature):
+    """`bmpc_samples` from the Python arguments, checked as the library checks it (ValueError)."""
+    w = np.asarray(w_viol, np.float64).reshape(-1)
+    if w.shape != (4,) or not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError("w_viol must be four finite prices >= 0 (friction, force box, moment box, line foot)")
+    T = float(temperature)
+    if not T > 0.0:
+        raise ValueError("temperature must be > 0 (inf: uniform weights)")
+    return _lib.CSamples(int(S), 0, (C.c_double * 4)(*w), T)
 
 
 def _ptr(a):
@@ -354,6 +383,37 @@ class BatchSolver:
             res[k] = res["summary"][:, i]
         return res
 
+    def evaluate_samples(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None,
+                         w_viol=(0, 0, 0, 0), temperature=float("inf")):
+        """S candidate plans per instance scored, ranked and blended in one call (`bmpc_evaluate_samples`, include/bmpc.h): inputs of
+        B instances as `evaluate` takes them -- nothing is replicated -- and `controls` (B,S,h,12), plan s of instance b.  Returns
+        NumPy arrays: cost (B,S), violation (B,S,4) as `evaluate` gives them for each plan; score (B,S) = cost + sum_c w_viol[c]
+        violation[..., c]; n_valid (B,) int32, the number of samples with a finite score; best (B,) int32, the lowest index of the
+        smallest valid score (-1: none); weights (B,S), the softmin weights exp(-(score - min) / temperature) normalised over the
+        valid samples (invalid ones exactly 0; temperature inf: uniform); u_mean (B,h,12), the weighted mean plan (MPPI's update;
+        at a small temperature the best plan); ess (B,), the effective sample size 1 / sum weights^2.  A sample with a non-finite
+        control gets NaN cost, violation and score and weight 0 and touches no other; an instance without a valid sample gets
+        best -1 and NaN u_mean and ess.  `max_batch` bounds B, not B S."""
+        return self._samples_host(x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, w_viol, temperature)
+
+    def _samples_host(self, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, w_viol, temperature, skip=()):
+        """The host entry of row "evaluate_samples" of `_EVAL_OPS`: as `_eval_host`, with S plans per instance."""
+        struct, entry, _, _, outputs = _EVAL_OPS["evaluate_samples"]
+        c32 = _samples_f32(controls, self.h)
+        B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
+        if c32.shape[0] != B:
+            raise ValueError(f"controls must have shape ({B}, S, {self.h}, 12), got {c32.shape}")
+        S = c32.shape[1]
+        smp = _samples_desc(S, w_viol, temperature)
+        x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h, finite=False)
+        if foot is None and foot_ref is None:
+            raise ValueError("foot is required unless foot_ref is given")
+        res = {k: None if k in skip else np.empty(_shape(shp, B, self.h, S), dt) for k, dt, shp in outputs}
+        inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
+        out = struct(**{k: _ptr(v) for k, v in res.items()})
+        _lib.check(getattr(self._lib, entry)(self._h, B, C.byref(inp), _ptr(c32), C.byref(smp), C.byref(out)))
+        return res
+
     def _eval_host(self, kind, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, act_tol=None, skip=()):
         """The host entry of row `kind` of `_EVAL_OPS`: host arrays marshalled as `solve` does, outputs allocated (None for those
         named in `skip`), one call.  Returns the dict of outputs."""
@@ -532,6 +592,42 @@ class BatchSolver:
         return self._eval_device("certify", x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref,
                                  dict(lam=lam, resid=resid, summary=summary, n_active=n_active, status=status), act_tol=act_tol,
                                  stream=stream)
+
+    def evaluate_samples_device(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None,
+                                w_viol=(0, 0, 0, 0), temperature=float("inf"), want=None, cost=None, violation=None, score=None,
+                                best=None, n_valid=None, weights=None, u_mean=None, ess=None, stream=None):
+        """`evaluate_samples` on CUDA(HIP) torch tensors of this solver's device (`bmpc_evaluate_samples_device`): inputs as
+        `evaluate_device` takes them, `controls` (B,S,h,12) float32.  Outputs are tensors cost (B,S), violation (B,S,4), score (B,S),
+        weights (B,S), u_mean (B,h,12), ess (B,) float64 and best (B,), n_valid (B,) int32: the caller's where passed, else allocated
+        -- all of them, or with `want` (names) only those named or passed; the others stay None and are not computed (a call that
+        wants no reduced output is one launch, else two).  Asynchronous on `stream` (default: torch's current stream) unless the
+        handle's scratch has to grow (include/bmpc.h); nothing crosses PCIe.  Returns the dict of outputs."""
+        import torch
+        struct, _, entry, _, outputs = _EVAL_OPS["evaluate_samples"]
+        h = self.h
+        dev = x_fb.device
+        if dev.type != "cuda" or dev.index != self.device:
+            raise ValueError(f"tensors must live on cuda:{self.device}")
+        B = x_fb.shape[0]
+        if controls.dim() != 4 or not 1 <= controls.shape[1] <= SAMPLES_MAX:
+            raise ValueError(f"controls must have shape ({B}, S, {h}, 12) with 1 <= S <= {SAMPLES_MAX}, got {tuple(controls.shape)}")
+        S = int(controls.shape[1])
+        smp = _samples_desc(S, w_viol, temperature)
+        given = dict(cost=cost, violation=violation, score=score, best=best, n_valid=n_valid, weights=weights, u_mean=u_mean, ess=ess)
+        if want is not None and not set(want) <= set(given):
+            raise ValueError(f"want names outputs among {sorted(given)}")
+        res = {}
+        for k, dt, shp in outputs:
+            t = given[k]
+            if t is None and (want is None or k in want):
+                t = torch.empty(_shape(shp, B, h, S), dtype=getattr(torch, dt), device=dev)
+            res[k] = t
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        inp = _lib.CInputs(*self._device_inputs(dev, B, x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref))
+        out = struct(**{k: _tensor_ptr(res[k], getattr(torch, dt), _shape(shp, B, h, S), dev) for k, dt, shp in outputs})
+        u = _tensor_ptr(controls, torch.float32, (B, S, h, 12), dev)
+        _lib.check(getattr(self._lib, entry)(self._h, B, C.byref(inp), u, C.byref(smp), C.byref(out), st))
+        return res
 
     def _eval_device(self, kind, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, given, act_tol=None, skip=(),
                      stream=None):
@@ -1081,6 +1177,24 @@ def evaluate_mpc(x_fb, t, foot, mpc, biped, contact, controls, half=None, device
     args, refs = _batch_of_one(x_fb, t, foot, mpc, contact, controls, x_ref, foot_ref)
     r = evaluate_mpc_batch(*args, mpc=mpc, biped=biped, half=half, device=device, **refs)
     return dict(cost=float(r["cost"][0]), objective=float(r["objective"][0]), violation=r["violation"][0], states=r["states"][0])
+
+
+def evaluate_samples_mpc_batch(x_fb, t, foot, contact, controls, mpc=None, biped=None, x_cmd=None, mu=None, phase=None, half=None,
+                               device=0, x_ref=None, foot_ref=None, w_viol=(0, 0, 0, 0), temperature=float("inf")):
+    """S candidate plans per instance scored, ranked and blended: `evaluate_mpc_batch`'s call surface (references in the reference's
+    orientation, the cached handle per horizon and device) with `controls` (B,S,h,12), the prices `w_viol` of the four violation
+    classes and the `temperature` of the softmin weights.  Returns the dict of `BatchSolver.evaluate_samples`.  Every check comes
+    before a solver handle can be created."""
+    from .params import MPC
+    mpc = mpc if mpc is not None else MPC()
+    c32 = _samples_f32(controls, int(mpc.h))
+    _samples_desc(c32.shape[1], w_viol, temperature)
+    xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
+    solver = _cached_solver(mpc, biped, half, device, None)
+    if phase is None:
+        phase = phase_indices(t, mpc.dt, mpc.h)
+    return solver.evaluate_samples(x_fb, foot, contact, phase, c32, x_cmd=x_cmd, mu=mu, x_ref=xr, foot_ref=fr, w_viol=w_viol,
+                                   temperature=temperature)
 
 
 def evaluate_grad_mpc_batch(x_fb, t, foot, contact, controls, mpc=None, biped=None, x_cmd=None, mu=None, phase=None, half=None,

@@ -8,6 +8,7 @@
 #include "bmpc_evaluate.hip"
 #include "bmpc_evaluate_grad.hip"
 #include "bmpc_certify.hip"
+#include "bmpc_evaluate_samples.hip"
 
 #include <chrono>
 #include <cmath>
@@ -227,6 +228,7 @@ struct bmpc_handle_s {
   DevBuf<char> stage[N_IN];         // host inputs on the device, one buffer per row of IN (stage_inputs, the low-level host entries)
   DevBuf<float> controls;           // host controls of the evaluation family; what an assembly launch stores
   DevBuf<double> eval_out;          // results of bmpc_evaluate (host pointers) on their way back
+  DevBuf<double> samples;           // bmpc_evaluate_samples*: scores / weights the reductions need and the caller did not ask for
   DevBuf<int32_t> status;           // the rescue pass's, where the caller asks for none
   DevBuf<double> dbg;
   DevBuf<float> ll_q, ll_qd, ll_pf, ll_u0, ll_tau;
@@ -521,9 +523,9 @@ int upload(bmpc_handle h, DevBuf<T>& buf, const U* src, size_t count, const U** 
 
 // The inputs of a solve, host arrays, onto the device through the handle's staging buffers (the synchronous host entries of the
 // evaluation family and bmpc_debug_assemble_inputs).  `controls`: host controls to stage with them, or null (the scratch array is
-// sized either way: the assembly launch stores there).  `din`: the descriptor of the copies.
-int stage_inputs(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, bmpc_inputs* din) {
-  const size_t n = (size_t)B, H = (size_t)h->dev.h, nu = n * OUT[O_U].w.count(H);
+// sized either way: the assembly launch stores there), `plans` of them per instance.  `din`: the descriptor of the copies.
+int stage_inputs(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, bmpc_inputs* din, size_t plans = 1) {
+  const size_t n = (size_t)B, H = (size_t)h->dev.h, nu = n * plans * OUT[O_U].w.count(H);
   HIP_TRY(h->controls.ensure(nu));
   for (int i = 0; i < N_IN; ++i) {
     const char* d;
@@ -542,8 +544,11 @@ int stage_inputs(bmpc_handle h, int B, const bmpc_inputs& in, const float* contr
 struct OutSlot { void* p; Width w; };
 template <size_t N> struct OutSlots { OutSlot s[N]; };
 
+// what an operation takes besides the inputs and the controls: certify's act_tol, the sampling descriptor of evaluate_samples
+struct EvalArg { double act_tol = 0.0; const bmpc_samples* smp = nullptr; };
+
 // `launch`: the operation's kernel on device-addressable inputs; `out`: one pointer per slot, in the table's order
-using EvalLaunch = int (*)(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, double act_tol, void* const* out,
+using EvalLaunch = int (*)(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const EvalArg& arg, void* const* out,
                            hipStream_t st);
 struct EvalOp { const char *null_out, *none_out; EvalLaunch launch; };
 
@@ -557,15 +562,50 @@ int launch_eval(bmpc_handle h, int B, const bmpc_inputs& in, const float* contro
   return BMPC_OK;
 }
 
-int launch_evaluate(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, double, void* const* o, hipStream_t st) {
+int launch_evaluate(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const EvalArg&, void* const* o, hipStream_t st) {
   return launch_eval<bmpc::evaluate_kernel>(h, B, in, controls, st, bmpc::EvalOut{(double*)o[0], (double*)o[1], (double*)o[2], (double*)o[3]});
 }
-int launch_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, double, void* const* o, hipStream_t st) {
+int launch_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const EvalArg&, void* const* o, hipStream_t st) {
   return launch_eval<bmpc::evaluate_grad_kernel>(h, B, in, controls, st, bmpc::GradOut{(double*)o[0], (double*)o[1], (double*)o[2]});
 }
-int launch_certify(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, double act_tol, void* const* o, hipStream_t st) {
-  return launch_eval<bmpc::certify_kernel>(h, B, in, controls, st, act_tol,
+int launch_certify(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const EvalArg& arg, void* const* o, hipStream_t st) {
+  return launch_eval<bmpc::certify_kernel>(h, B, in, controls, st, arg.act_tol,
                                            bmpc::CertOut{(double*)o[0], (double*)o[1], (double*)o[2], (int32_t*)o[3], (int32_t*)o[4]});
+}
+
+// evaluate_samples: the per-sample kernel over B ceil(S / C) groups, C samples each (bmpc::eval_samples_per_group), then -- where a
+// reduced output is wanted -- the per-instance reductions behind it on the same stream.  The reductions read the scores and the
+// weights from the device: where the caller wants neither array, they live in the handle's scratch, grown on demand (a call
+// that has to grow it is not asynchronous: the old block is freed).  o: the slots of bmpc_samples_out, in its order.
+int launch_evaluate_samples(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const EvalArg& arg, void* const* o,
+                            hipStream_t st) {
+  const bmpc_samples& smp = *arg.smp;
+  const size_t n = (size_t)B * (size_t)smp.S;
+  const bool reduce = o[3] || o[4] || o[5] || o[6] || o[7];
+  double *score = (double*)o[2], *weights = (double*)o[5];
+  const size_t need = (score ? 0 : n) + (reduce && !weights ? n : 0);
+  if (need) {
+    HIP_TRY(h->samples.ensure(need));
+    if (!score) score = h->samples.p;
+    if (reduce && !weights) weights = h->samples.p + (need - n);
+  }
+  const int C = bmpc::eval_samples_per_group(B, smp.S);
+  const long long groups = (long long)B * (((long long)smp.S + C - 1) / C);
+  const long long blocks = (groups * bmpc::eval_lanes(h->params.h) + bmpc::EVAL_NT - 1) / bmpc::EVAL_NT;
+  if (blocks > 0x7fffffffLL) return fail(BMPC_ERR_INVALID, "B x S = %zu plans are more than one launch holds", n);
+  bmpc::SamplesPrice price;
+  for (int c = 0; c < 4; ++c) price.w[c] = smp.w_viol[c];
+  hipLaunchKernelGGL(bmpc::evaluate_samples_kernel, dim3((unsigned)blocks), dim3(bmpc::EVAL_NT), 0, st,
+                     bmpc::eval_params(h->params, h->dev.Iinv), B, (int)smp.S, C, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd, in.mu,
+                     in.x_ref, in.foot_ref, controls, price, bmpc::SamplesOut{(double*)o[0], (double*)o[1], score});
+  HIP_TRY(hipGetLastError());
+  if (reduce) {
+    hipLaunchKernelGGL(bmpc::sample_reduce_kernel, dim3((unsigned)B), dim3(bmpc::REDUCE_NT), 0, st, (int)h->params.h, (int)smp.S,
+                       smp.temperature, (const double*)score, controls,
+                       bmpc::ReduceOut{(int32_t*)o[3], (int32_t*)o[4], weights, (double*)o[6], (double*)o[7]});
+    HIP_TRY(hipGetLastError());
+  }
+  return BMPC_OK;
 }
 
 const EvalOp EVALUATE = {"null bmpc_eval_out", "bmpc_eval_out: at least one of cost, objective, states, violation must be non-null",
@@ -574,6 +614,9 @@ const EvalOp EVALUATE_GRAD = {"null bmpc_grad_out", "bmpc_grad_out: at least one
                               launch_evaluate_grad};
 const EvalOp CERTIFY = {"null bmpc_cert_out", "bmpc_cert_out: at least one of lam, resid, summary, n_active, status must be non-null",
                         launch_certify};
+const EvalOp EVALUATE_SAMPLES = {"null bmpc_samples_out",
+                                 "bmpc_samples_out: at least one of cost, violation, score, best, n_valid, weights, u_mean, ess must be non-null",
+                                 launch_evaluate_samples};
 
 // the slot tables, in the member order of the descriptors (include/bmpc.h); a null descriptor gives all-null slots
 OutSlots<4> slots_of(const bmpc_eval_out* out) {
@@ -587,6 +630,25 @@ OutSlots<3> slots_of(const bmpc_grad_out* out) {
 OutSlots<5> slots_of(const bmpc_cert_out* out) {
   const bmpc_cert_out o = out ? *out : bmpc_cert_out{};
   return {{{o.lam, {0, 36, 8}}, {o.resid, {0, 12, 8}}, {o.summary, {4, 0, 8}}, {o.n_active, {1, 0, 4}}, {o.status, {1, 0, 4}}}};
+}
+
+// (per-sample arrays: S entries per instance; S = 1 where the sampling descriptor is null or out of range -- the entry refuses it)
+OutSlots<8> slots_of(const bmpc_samples_out* out, const bmpc_samples* smp) {
+  const bmpc_samples_out o = out ? *out : bmpc_samples_out{};
+  const size_t S = smp && smp->S >= 1 && smp->S <= bmpc::SAMPLES_MAX ? (size_t)smp->S : 1;
+  return {{{o.cost, {S, 0, 8}}, {o.violation, {4 * S, 0, 8}}, {o.score, {S, 0, 8}}, {o.best, {1, 0, 4}}, {o.n_valid, {1, 0, 4}},
+           {o.weights, {S, 0, 8}}, {o.u_mean, {0, 12, 8}}, {o.ess, {1, 0, 8}}}};
+}
+
+// the sampling descriptor of bmpc_evaluate_samples*, checked before anything else of the call (as certify's act_tol is)
+int check_samples(const bmpc_samples* smp) {
+  if (!smp) return fail(BMPC_ERR_INVALID, "null bmpc_samples");
+  if (smp->S < 1 || smp->S > bmpc::SAMPLES_MAX) return fail(BMPC_ERR_INVALID, "bmpc_samples: S = %d outside [1, %d]", (int)smp->S, bmpc::SAMPLES_MAX);
+  for (int c = 0; c < 4; ++c)
+    if (!(smp->w_viol[c] >= 0.0 && smp->w_viol[c] <= 1.7976931348623157e308))
+      return fail(BMPC_ERR_INVALID, "bmpc_samples: w_viol[%d] must be finite and >= 0", c);
+  if (!(smp->temperature > 0.0)) return fail(BMPC_ERR_INVALID, "bmpc_samples: temperature must be > 0 (+inf allowed)");
+  return BMPC_OK;
 }
 
 // what every entry checks before a device is touched (and before the handle is read): an error code (< 0), BMPC_OK when there is
@@ -606,19 +668,19 @@ int check_eval(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, co
 
 // the device entry: everything device-addressable, asynchronous on `stream`
 template <size_t N>
-int eval_device(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol,
+int eval_device(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const EvalArg& arg,
                 const void* out, const OutSlots<N>& slots, void* stream) {
   if (int rc = check_eval(op, h, B, in, controls, out, slots); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   void* d[N];
   for (size_t i = 0; i < N; ++i) d[i] = slots.s[i].p;
-  return op.launch(h, B, *in, controls, act_tol, d, pick_stream(h, stream));
+  return op.launch(h, B, *in, controls, arg, d, pick_stream(h, stream));
 }
 
 // the host entry: the wanted outputs are carved out of the handle's eval_out block (each on an 8-byte boundary), the inputs
 // staged, the kernel launched on the copies, the outputs copied back; synchronous on the handle's own stream
 template <size_t N>
-int eval_host(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol,
+int eval_host(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const EvalArg& arg,
               const void* out, const OutSlots<N>& slots) {
   if (int rc = check_eval(op, h, B, in, controls, out, slots); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
@@ -632,11 +694,11 @@ int eval_host(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, con
   }
   HIP_TRY(h->eval_out.ensure(tot));
   bmpc_inputs din;
-  if (int rc = stage_inputs(h, B, *in, controls, &din); rc != BMPC_OK) return rc;
+  if (int rc = stage_inputs(h, B, *in, controls, &din, arg.smp ? (size_t)arg.smp->S : 1); rc != BMPC_OK) return rc;
   hipStream_t st = h->stream;
   void* d[N];
   for (size_t i = 0; i < N; ++i) d[i] = slots.s[i].p ? h->eval_out.p + off[i] : nullptr;
-  if (int rc = op.launch(h, B, din, h->controls.p, act_tol, d, st); rc != BMPC_OK) return rc;
+  if (int rc = op.launch(h, B, din, h->controls.p, arg, d, st); rc != BMPC_OK) return rc;
   for (size_t i = 0; i < N; ++i)
     if (slots.s[i].p) HIP_TRY(hipMemcpyAsync(slots.s[i].p, d[i], bytes[i], hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -933,30 +995,42 @@ int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* fo
 // ---- the evaluation family (helpers above): evaluation of given controls, the gradient of its cost, the KKT certificate
 
 int bmpc_evaluate_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out, void* stream) {
-  return eval_device(EVALUATE, h, B, in, controls, 0.0, out, slots_of(out), stream);
+  return eval_device(EVALUATE, h, B, in, controls, {}, out, slots_of(out), stream);
 }
 
 int bmpc_evaluate(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_eval_out* out) {
-  return eval_host(EVALUATE, h, B, in, controls, 0.0, out, slots_of(out));
+  return eval_host(EVALUATE, h, B, in, controls, {}, out, slots_of(out));
 }
 
 int bmpc_evaluate_grad_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_grad_out* out, void* stream) {
-  return eval_device(EVALUATE_GRAD, h, B, in, controls, 0.0, out, slots_of(out), stream);
+  return eval_device(EVALUATE_GRAD, h, B, in, controls, {}, out, slots_of(out), stream);
 }
 
 int bmpc_evaluate_grad(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_grad_out* out) {
-  return eval_host(EVALUATE_GRAD, h, B, in, controls, 0.0, out, slots_of(out));
+  return eval_host(EVALUATE_GRAD, h, B, in, controls, {}, out, slots_of(out));
 }
 
 int bmpc_certify_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol, const bmpc_cert_out* out,
                         void* stream) {
   if (act_tol != act_tol) return fail(BMPC_ERR_INVALID, "act_tol is NaN");
-  return eval_device(CERTIFY, h, B, in, controls, act_tol, out, slots_of(out), stream);
+  return eval_device(CERTIFY, h, B, in, controls, {act_tol}, out, slots_of(out), stream);
 }
 
 int bmpc_certify(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol, const bmpc_cert_out* out) {
   if (act_tol != act_tol) return fail(BMPC_ERR_INVALID, "act_tol is NaN");
-  return eval_host(CERTIFY, h, B, in, controls, act_tol, out, slots_of(out));
+  return eval_host(CERTIFY, h, B, in, controls, {act_tol}, out, slots_of(out));
+}
+
+int bmpc_evaluate_samples_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_samples* smp,
+                                 const bmpc_samples_out* out, void* stream) {
+  if (int rc = check_samples(smp); rc != BMPC_OK) return rc;
+  return eval_device(EVALUATE_SAMPLES, h, B, in, controls, {0.0, smp}, out, slots_of(out, smp), stream);
+}
+
+int bmpc_evaluate_samples(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_samples* smp,
+                          const bmpc_samples_out* out) {
+  if (int rc = check_samples(smp); rc != BMPC_OK) return rc;
+  return eval_host(EVALUATE_SAMPLES, h, B, in, controls, {0.0, smp}, out, slots_of(out, smp));
 }
 
 static bmpc::LowLevelParams ll_params(const bmpc_params& p) {

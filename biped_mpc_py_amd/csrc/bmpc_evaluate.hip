@@ -41,6 +41,18 @@ constexpr int EVAL_NT = 256;                   // lanes per workgroup (4 waves; 
 // lanes per instance at horizon h (one lane per step, rounded up to a power of two that divides the wave): THE rule for the
 // kernels (eval_lane), the launch grid (bmpc_capi.hip) and the emulation's grid (tests/emu)
 constexpr int eval_lanes(const int h) { return h <= 16 ? 16 : (h <= 32 ? 32 : 64); }
+// samples per lane group of evaluate_samples_kernel (bmpc_evaluate_samples.hip), where a group owns one instance and a run of its
+// samples: THE rule for the launch grid (bmpc_capi.hip), the kernel (handed in as `C`) and the emulation's grid.
+// As many as SPG_MAX, so that the set-up is shared widely; halved while a group would own no sample in its upper half (small S),
+// and, down to SPG_MIN, while the launch would have fewer than SPG_GROUPS groups: 8192 groups of 16 lanes are 2048 waves, two per
+// SIMD on 256 CUs -- what the kernel's registers admit --, so a small B with a large S still fills the device.
+constexpr int SPG_MAX = 32, SPG_MIN = 4;
+constexpr long long SPG_GROUPS = 8192;
+constexpr int eval_samples_per_group(const long long B, const long long S) {
+  int C = SPG_MAX;
+  while (C > 1 && (C / 2 >= S || (C > SPG_MIN && B * ((S + C - 1) / C) < SPG_GROUPS))) C /= 2;
+  return C;
+}
 
 struct EvalParams {
   int h, half;

@@ -472,6 +472,69 @@ int bmpc_certify_device(bmpc_handle h, int B, const bmpc_inputs* in, const float
 int bmpc_certify(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, double act_tol, const bmpc_cert_out* out);
 
 /*
+ * S candidate plans per instance in one launch, ranked and blended on the device (added under ABI 13; BMPC_ABI_VERSION is unchanged
+ * because the addition is purely additive, so a caller detects it by the symbol, e.g. dlsym(lib, "bmpc_evaluate_samples_device")).
+ * What a sampling controller holds is B situations and S candidate plans for each -- a nominal plan plus noise, last period's plan
+ * shifted, a policy's proposals.  This operation scores them all, picks the best and forms the softmin-weighted mean plan (the
+ * update of MPPI and of predictive sampling) without replicating an input and without leaving the device.  Inputs: those of
+ * bmpc_evaluate* for B instances, and
+ *   controls [B][S][h][12] fp32: plan s of instance b, row k = [f1 f2 m1 m2]
+ *   smp      S, the prices w_viol of the four violation classes and the temperature of the weights (below)
+ * Per-sample outputs, each optional (NULL = not wanted; at least one output of the struct must be given), fp64:
+ *   cost      [S]     what bmpc_evaluate* returns as `cost` for the inputs of instance b and the controls controls[b][s]: the same
+ *   violation [S][4]  arithmetic (fp64 on the widened fp32 inputs; references supplied or generated; per-step mu), likewise
+ *   score     [S]     cost + w_viol[0] violation[0] + w_viol[1] violation[1] + w_viol[2] violation[2] + w_viol[3] violation[3],
+ *                     added in that order
+ * A sample's cost, violation and score depend on nothing but its instance's inputs and its own controls: not on B, S, b or s, nor
+ * on how the launch groups the samples.  A sample is VALID iff its score is finite.  A non-finite control entry makes that sample's
+ * cost, violation and score NaN and touches no other sample; a bad instance (as for the evaluation: a non-finite input or
+ * reference entry, a reference pitch within fp32 rounding of +-90 degrees) makes every sample of it NaN.
+ * Per-instance reductions, each optional:
+ *   n_valid  int32: the number of valid samples
+ *   best     int32: the smallest index among the valid samples of smallest score; -1 if n_valid is 0
+ *   weights  [S] fp64: e_s / sum_s e_s with e_s = exp(-(score_s - m) / temperature), m the best score, for valid samples; an invalid
+ *            sample has e_s and its weight exactly +0
+ *   u_mean   [h][12] fp64: sum_s weights_s controls[b][s], accumulated in fp64; an invalid sample's controls do not enter it
+ *   ess      fp64: 1 / sum_s weights_s^2, the effective sample size (1 .. n_valid)
+ * If n_valid is 0 the weights are all +0 and u_mean and ess are NaN.  A temperature of +inf gives uniform weights 1 / n_valid.
+ * The reduced values of an instance do not depend on B or on its place in the batch and repeat bit for bit from run to run: no
+ * floating-point atomics, every sum in an order fixed by (S, h) alone.
+ *   bmpc_evaluate_samples_device   DEVICE pointers, asynchronous on `stream` (same rules as bmpc_evaluate_device); nothing is
+ *                                  copied.  Two launches on that stream: the per-sample kernel and, where a reduced output is
+ *                                  wanted, the reductions behind it.
+ *   bmpc_evaluate_samples          HOST pointers, synchronous (staged through the handle's own stream)
+ * Checked before a device is touched, each BMPC_ERR_INVALID: a NULL `smp`, S outside [1, 65536], a w_viol entry that is NaN,
+ * negative or infinite, a temperature that is NaN or <= 0 (these first); a NULL handle, `in`, `controls` or `out`; all eight outputs
+ * NULL; foot == NULL without foot_ref; B outside [0, max_batch].  B = 0 succeeds.  max_batch bounds B, not B S.
+ * The handle's parameter block is read (bmpc_set_params takes effect) and none of its per-solve state is touched, as for
+ * bmpc_evaluate*: warm start, dispatch order, event pair and I/O block are left alone and bmpc_last_kernel_ms keeps reporting the
+ * last SOLVE.  The reductions read the scores and the weights on the device; where the caller asks for a reduced output but not for
+ * `score` or `weights`, those live in a scratch buffer owned by the handle and grown on demand.  A bmpc_evaluate_samples_device call
+ * that has to GROW that scratch is not asynchronous (the old block is freed, which waits for the device), and calls that use the
+ * scratch of one handle must be ordered on one stream; a caller that passes both `score` and `weights` never touches it.
+ */
+typedef struct bmpc_samples {
+  int32_t S;            /* samples per instance, 1 .. 65536 */
+  int32_t reserved0;
+  double  w_viol[4];    /* finite, >= 0: price of the largest violation per row class (friction, force box, moment box, line foot) */
+  double  temperature;  /* > 0, +inf allowed (uniform weights) */
+} bmpc_samples;
+typedef struct bmpc_samples_out {     /* each NULL = not wanted; at least one non-NULL */
+  double*  cost;       /* [B][S]     */
+  double*  violation;  /* [B][S][4]  */
+  double*  score;      /* [B][S]     */
+  int32_t* best;       /* [B]        */
+  int32_t* n_valid;    /* [B]        */
+  double*  weights;    /* [B][S]     */
+  double*  u_mean;     /* [B][h][12] */
+  double*  ess;        /* [B]        */
+} bmpc_samples_out;
+int bmpc_evaluate_samples_device(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_samples* smp,
+                                 const bmpc_samples_out* out, void* stream);
+int bmpc_evaluate_samples(bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const bmpc_samples* smp,
+                          const bmpc_samples_out* out);
+
+/*
  * The step either side of the MPC solve, batched; HOST pointers, synchronous.
  *   bmpc_foot_position_world  replaces getFootPositionWorld (REF:406-424, with getFootPositionBody REF:367-404):
  *       x_fb [B][12], q [B][10] joint angles  ->  pf_w [B][6]
