@@ -29,6 +29,7 @@ EXPORTS = (
     "bmpc_plant_default", "bmpc_plant_step", "bmpc_plant_step_device", "bmpc_simulate_device",
     "bmpc_plant_step_body", "bmpc_plant_step_body_device", "bmpc_simulate_body_device",
     "bmpc_plant_step_ground", "bmpc_plant_step_ground_device", "bmpc_simulate_ground_device",
+    "bmpc_plant_rollout_samples", "bmpc_plant_rollout_samples_device",
 )
 
 
@@ -101,6 +102,19 @@ class CSamples(C.Structure):
 class CSamplesOut(C.Structure):
     """`bmpc_samples_out` of include/bmpc.h: per-sample values and per-instance reductions, each optional (NULL: not wanted)."""
     _fields_ = [(n, C.c_void_p) for n in ("cost", "violation", "score", "best", "n_valid", "weights", "u_mean", "ess")]
+
+
+class CRolloutPrice(C.Structure):
+    """`bmpc_rollout_price` of include/bmpc.h: samples per instance, the prices of the score, the temperature, the fall thresholds and
+    the floor of the demand."""
+    _fields_ = [("S", C.c_int32), ("reserved0", C.c_int32)] + [(n, C.c_double) for n in ("w_fall", "w_slip", "w_unloaded", "temperature",
+                                                                                      "tilt_max", "z_min", "fz_floor")]
+
+
+class CRolloutOut(C.Structure):
+    """`bmpc_rollout_out` of include/bmpc.h: per-sample values and per-instance reductions, each optional (NULL: not wanted)."""
+    _fields_ = [(n, C.c_void_p) for n in ("cost", "score", "x_end", "foot_end", "x_traj", "first_fall", "max_tilt", "min_z", "first_slip",
+                                           "slip_periods", "unloaded_periods", "mu_demand", "best", "n_valid", "weights", "u_mean", "ess")]
 
 
 class BmpcError(RuntimeError):
@@ -224,6 +238,10 @@ def load():
     lib.bmpc_plant_step_ground_device.argtypes = [vp, ip, C.POINTER(CPlant), C.POINTER(CPlantBody), C.POINTER(CPlantGround)] + [vp] * 9
     lib.bmpc_simulate_ground_device.argtypes = [vp, ip, ip, C.POINTER(CPlant), C.POINTER(CPlantBody), C.POINTER(CPlantGround), vp, vp,
                                                 vp, C.POINTER(CGait)] + [vp] * 8 + [C.POINTER(CSimOutcome), C.POINTER(CGroundOut), vp]
+    rollout = [vp, ip] + [vp] * 7 + [C.POINTER(CPlant), C.POINTER(CPlantBody), C.POINTER(CPlantGround), C.POINTER(CRolloutPrice),
+                                     C.POINTER(CRolloutOut)]
+    lib.bmpc_plant_rollout_samples.argtypes = rollout
+    lib.bmpc_plant_rollout_samples_device.argtypes = rollout + [vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name != "bmpc_last_error":

@@ -1033,6 +1033,132 @@ class BatchSolver:
             *traj, None if co is None else C.byref(co), st))
         return out
 
+    # ---- S candidate plans per instance on the plant (bmpc_plant_rollout_samples*) ---------------------
+    _ROLLOUT_OUTPUTS = (("cost", "float64", ("B", "S")), ("score", "float64", ("B", "S")), ("x_end", "float32", ("B", "S", 12)),
+                        ("foot_end", "float32", ("B", "S", 6)), ("x_traj", "float32", ("B", "S", "h", 12)),
+                        ("first_fall", "int32", ("B", "S")), ("max_tilt", "float32", ("B", "S")), ("min_z", "float32", ("B", "S")),
+                        ("first_slip", "int32", ("B", "S")), ("slip_periods", "int32", ("B", "S", 2)),
+                        ("unloaded_periods", "int32", ("B", "S", 2)), ("mu_demand", "float32", ("B", "S")), ("best", "int32", ("B",)),
+                        ("n_valid", "int32", ("B",)), ("weights", "float64", ("B", "S")), ("u_mean", "float64", ("B", "h", 12)),
+                        ("ess", "float64", ("B",)))
+    _ROLLOUT_GROUND_ONLY = ("first_slip", "slip_periods", "unloaded_periods", "mu_demand")
+
+    @classmethod
+    def _rollout_opts(cls, S, push_from, push_steps, integrator, substeps, move_feet, ground, fall, fz_floor, w_fall, w_slip, w_unloaded,
+                      temperature, want):
+        """(`bmpc_plant`, `bmpc_rollout_price`, the names of the wanted outputs) from the keyword arguments of the roll-out methods,
+        checked as the library checks them (ValueError).  `want` None: every output there is (the ground's four only with a ground)."""
+        plant = cls._plant(integrator, substeps, move_feet, push_from, push_steps)
+        cls._ground_mu(ground)
+        w = [float(v) for v in (w_fall, w_slip, w_unloaded)]
+        if not all(np.isfinite(v) and v >= 0.0 for v in w):
+            raise ValueError("w_fall, w_slip and w_unloaded must be finite and >= 0")
+        T = float(temperature)
+        if not T > 0.0:
+            raise ValueError("temperature must be > 0 (inf: uniform weights)")
+        try:
+            tilt_max, z_min = (float(v) for v in fall)
+        except (TypeError, ValueError):
+            raise ValueError("fall must be a (tilt_max, z_min) pair") from None
+        if tilt_max != tilt_max or z_min != z_min:
+            raise ValueError("fall thresholds must not be NaN")
+        if not float(fz_floor) >= 0.0:
+            raise ValueError("fz_floor must be >= 0 and not NaN")
+        names = [k for k, _, _ in cls._ROLLOUT_OUTPUTS]
+        if want is None:
+            want = [k for k in names if ground is not None or k not in cls._ROLLOUT_GROUND_ONLY]
+        want = list(want)
+        if not want or not set(want) <= set(names):
+            raise ValueError(f"want names at least one output among {names}")
+        if ground is None and set(want) & set(cls._ROLLOUT_GROUND_ONLY):
+            raise ValueError(f"{', '.join(cls._ROLLOUT_GROUND_ONLY)} need a ground")
+        if not 1 <= int(S) <= SAMPLES_MAX:
+            raise ValueError(f"controls must hold 1 <= S <= {SAMPLES_MAX} plans per instance")
+        return plant, _lib.CRolloutPrice(int(S), 0, *w, T, tilt_max, z_min, float(fz_floor)), want
+
+    def plant_rollout_samples(self, x_fb, foot, contact, controls, x_cmd=None, x_ref=None, push=None, push_from=0, push_steps=0,
+                              integrator="rk4", substeps=4, move_feet=True, body=None, ground=None, fall=(float("inf"), float("-inf")),
+                              fz_floor=0.0, w_fall=0.0, w_slip=0.0, w_unloaded=0.0, temperature=float("inf"), want=None):
+        """What the rigid body makes of S whole plans per instance, in one launch (`bmpc_plant_rollout_samples`, include/bmpc.h):
+        x_fb (B,12), foot (B,6), contact (B,h,2) -- row k holds over period k --, controls (B,S,h,12), plan s of instance b; nothing
+        is replicated and `max_batch` bounds B, not B S.  Per period the plant of `plant_step` integrates the plan's control (through
+        the `ground`, where given; under `push` (B,6) in periods push_from <= k < push_from + push_steps), the new state is stored in
+        fp32 and the next period starts from it; with `move_feet` a leg whose contact bit goes 0 -> 1 from row k to row k + 1 lands
+        on the swing controller's target at that state.  `body`, `ground`: as for `plant_step`; `fall` = (tilt_max, z_min) and
+        `fz_floor`: as for `simulate_device`; x_cmd (B,12): per-instance commands; x_ref (B,h,12): the state reference in the kernel
+        layout (None: generated as the solve generates it).  Returns a dict of NumPy arrays -- all of them, or those named in `want`:
+        cost (B,S) = sum_k sum_i Q_i (x_k,i - x_ref_k,i)^2 + R_i u_k,i^2 on the stored states and the COMMANDED controls; score (B,S)
+        = cost + w_fall [fell] + w_slip (periods a leg slipped) + w_unloaded (periods a stance leg was unloaded); x_end (B,S,12),
+        foot_end (B,S,6), x_traj (B,S,h,12) float32; first_fall (B,S) int32, max_tilt, min_z (B,S) float32; with a ground first_slip
+        (B,S), slip_periods, unloaded_periods (B,S,2) int32 and mu_demand (B,S) float32; and per instance best, n_valid (B,) int32,
+        weights (B,S), u_mean (B,h,12), ess (B,) as `evaluate_samples` forms them from these scores at `temperature`.  A plan with a
+        non-finite control, or one whose plant step goes bad, has a NaN state from that period on, NaN cost and score, first_fall at
+        that period and weight 0; a bad instance (non-finite x_fb / foot / push / reference, bad body, mu NaN or negative) makes
+        every plan of it so."""
+        c32 = _samples_f32(controls, self.h)
+        B, S, h = c32.shape[0], c32.shape[1], self.h
+        plant, price, want = self._rollout_opts(S, push_from, push_steps, integrator, substeps, move_feet, ground, fall, fz_floor,
+                                                w_fall, w_slip, w_unloaded, temperature, want)
+        arrs = []
+        for name, v, shp in (("x_fb", x_fb, (B, 12)), ("foot", foot, (B, 6)), ("x_cmd", x_cmd, (B, 12)), ("x_ref", x_ref, (B, h, 12)),
+                             ("push", push, (B, 6))):
+            if v is not None:
+                v = np.asarray(v)
+                if v.shape != shp:
+                    raise ValueError(f"{name} must have shape {shp}, not {v.shape}")
+                v = np.ascontiguousarray(v, np.float32)
+            elif name in ("x_fb", "foot"):
+                raise ValueError(f"{name} is required")
+            arrs.append(v)
+        xf, ft, xc, xr, ps = arrs
+        con = _contact_u8(contact, B, h)
+        cb, keep = (None, None) if body is None else self._body_host(body, B)
+        cg, keep_g = (None, None) if ground is None else self._ground_host(ground, B)
+        res = {k: np.empty(_shape(shp, B, h, S), dt) for k, dt, shp in self._ROLLOUT_OUTPUTS if k in want}
+        out = _lib.CRolloutOut(**{k: _ptr(v) for k, v in res.items()})
+        _lib.check(self._lib.bmpc_plant_rollout_samples(
+            self._h, B, _ptr(xf), _ptr(ft), _ptr(con), _ptr(xc), _ptr(xr), _ptr(ps), _ptr(c32), C.byref(plant),
+            None if cb is None else C.byref(cb), None if cg is None else C.byref(cg), C.byref(price), C.byref(out)))
+        del keep, keep_g
+        return res
+
+    def plant_rollout_samples_device(self, x_fb, foot, contact, controls, x_cmd=None, x_ref=None, push=None, push_from=0, push_steps=0,
+                                     integrator="rk4", substeps=4, move_feet=True, body=None, ground=None,
+                                     fall=(float("inf"), float("-inf")), fz_floor=0.0, w_fall=0.0, w_slip=0.0, w_unloaded=0.0,
+                                     temperature=float("inf"), want=None, stream=None):
+        """`plant_rollout_samples` on CUDA(HIP) torch tensors of this solver's device (`bmpc_plant_rollout_samples_device`): float32
+        x_fb (B,12), foot (B,6), controls (B,S,h,12), x_cmd (B,12), x_ref (B,h,12), push (B,6), uint8 contact (B,h,2); `body` and
+        `ground` of float64 device tensors as for `plant_step_device`.  The outputs -- all of them, or those named in `want` -- are
+        allocated here; one launch, and a second for the per-instance reductions where one of them is wanted.  Asynchronous on
+        `stream` (default: torch's current stream) unless the handle's scratch has to grow (include/bmpc.h); nothing crosses PCIe.
+        Returns the dict of output tensors."""
+        import torch
+        h = self.h
+        if x_fb.dim() != 2 or controls.dim() != 4:
+            raise ValueError(f"x_fb must have shape (B, 12) and controls (B, S, {h}, 12)")
+        B, S = x_fb.shape[0], int(controls.shape[1])
+        plant, price, want = self._rollout_opts(S, push_from, push_steps, integrator, substeps, move_feet, ground, fall, fz_floor,
+                                                w_fall, w_slip, w_unloaded, temperature, want)
+        dev = x_fb.device
+        if dev.type != "cuda" or dev.index != self.device:
+            raise ValueError(f"tensors must live on cuda:{self.device}")
+        args = [_tensor_ptr(t, dt, shp, dev) for t, dt, shp in (
+            (x_fb, torch.float32, (B, 12)), (foot, torch.float32, (B, 6)), (contact, torch.uint8, (B, h, 2)),
+            (x_cmd, torch.float32, (B, 12)), (x_ref, torch.float32, (B, h, 12)), (push, torch.float32, (B, 6)),
+            (controls, torch.float32, (B, S, h, 12)))]
+        cb = None if body is None else self._body_device(body, B, dev)
+        cg = None if ground is None else self._ground_device(ground, B, dev)
+        res = {k: torch.empty(_shape(shp, B, h, S), dtype=getattr(torch, dt), device=dev) for k, dt, shp in self._ROLLOUT_OUTPUTS
+               if k in want}
+        if B == 0:                                       # (nothing to do, and an empty tensor has no address to hand over)
+            return res
+        out = _lib.CRolloutOut(**{k: v.data_ptr() for k, v in res.items()})
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        _lib.check(self._lib.bmpc_plant_rollout_samples_device(
+            self._h, B, *args, C.byref(plant), None if cb is None else C.byref(cb), None if cg is None else C.byref(cg), C.byref(price),
+            C.byref(out), st))
+        return res
+
     def last_kernel_ms(self):
         ms = C.c_float(-1.0)
         _lib.check(self._lib.bmpc_last_kernel_ms(self._h, C.byref(ms)))

@@ -9,6 +9,7 @@
 #include "bmpc_evaluate_grad.hip"
 #include "bmpc_certify.hip"
 #include "bmpc_evaluate_samples.hip"
+#include "bmpc_plant_rollout.hip"
 
 #include <chrono>
 #include <cmath>
@@ -238,6 +239,7 @@ struct bmpc_handle_s {
   DevBuf<double> ground_mu;                // bmpc_plant_step_ground: the host ground on the device, and what it records on its way back
   DevBuf<float> ground_ua;
   DevBuf<uint8_t> ground_fl;
+  DevBuf<double> rollout_in, rollout_out;  // bmpc_plant_rollout_samples: the host arrays on the device, and the results on their way back
   long long* prof_dev = nullptr;   // optional cycle-stamp buffer (bmpc_debug_set_profile)
   // receding-horizon warm start (bmpc_set_warm_start): solver state of the last batch, kept on the device
   DevBuf<double> warm;
@@ -1463,6 +1465,146 @@ int bmpc_simulate_ground_device(bmpc_handle h, int B, int steps, const bmpc_plan
                                 const bmpc_ground_out* gout, void* stream) {
   return simulate(h, B, steps, plant, body, ground, x_fb, foot, t, gait, x_cmd, mu, push, u0_traj, x_traj, foot_traj, iters_traj,
                   status_any, outcome, gout, stream);
+}
+
+// ---- S candidate plans per instance on the plant (bmpc_plant_rollout.hip)
+
+// the outputs of bmpc_rollout_out in its member order: elements per instance (S: per sample) and bytes per element; a null
+// descriptor gives all-null slots.  Slots 8 .. 11 need a ground, 12 .. 16 are sample_reduce_kernel's.
+constexpr int RO_SCORE = 1, RO_GROUND = 8, RO_REDUCED = 12, RO_WEIGHTS = 14, N_RO = 17;
+static OutSlots<N_RO> rollout_slots(const bmpc_rollout_out* out, const bmpc_rollout_price* price) {
+  const bmpc_rollout_out o = out ? *out : bmpc_rollout_out{};
+  const size_t S = price && price->S >= 1 && price->S <= bmpc::SAMPLES_MAX ? (size_t)price->S : 1;
+  return {{{o.cost, {S, 0, 8}}, {o.score, {S, 0, 8}}, {o.x_end, {12 * S, 0, 4}}, {o.foot_end, {6 * S, 0, 4}}, {o.x_traj, {0, 12 * S, 4}},
+           {o.first_fall, {S, 0, 4}}, {o.max_tilt, {S, 0, 4}}, {o.min_z, {S, 0, 4}}, {o.first_slip, {S, 0, 4}},
+           {o.slip_periods, {2 * S, 0, 4}}, {o.unloaded_periods, {2 * S, 0, 4}}, {o.mu_demand, {S, 0, 4}}, {o.best, {1, 0, 4}},
+           {o.n_valid, {1, 0, 4}}, {o.weights, {S, 0, 8}}, {o.u_mean, {0, 12, 8}}, {o.ess, {1, 0, 8}}}};
+}
+
+// What both entries check, in the order of include/bmpc.h: an error code (< 0), BMPC_OK when there is nothing to do, 1 to go on.
+static int rollout_check(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact, const float* controls,
+                         const bmpc_plant* plant, const bmpc_plant_ground* ground, const bmpc_rollout_price* price,
+                         const bmpc_rollout_out* out, const OutSlots<N_RO>& slots, bmpc_plant* o) {
+  if (!price) return fail(BMPC_ERR_INVALID, "null bmpc_rollout_price");
+  if (price->S < 1 || price->S > bmpc::SAMPLES_MAX)
+    return fail(BMPC_ERR_INVALID, "bmpc_rollout_price: S = %d outside [1, %d]", (int)price->S, bmpc::SAMPLES_MAX);
+  const double w[3] = {price->w_fall, price->w_slip, price->w_unloaded};
+  for (int c = 0; c < 3; ++c)
+    if (!(w[c] >= 0.0 && w[c] <= 1.7976931348623157e308))
+      return fail(BMPC_ERR_INVALID, "bmpc_rollout_price: w_fall, w_slip and w_unloaded must be finite and >= 0");
+  if (!(price->temperature > 0.0)) return fail(BMPC_ERR_INVALID, "bmpc_rollout_price: temperature must be > 0 (+inf allowed)");
+  if (price->tilt_max != price->tilt_max || price->z_min != price->z_min)
+    return fail(BMPC_ERR_INVALID, "bmpc_rollout_price: thresholds tilt_max and z_min must not be NaN");
+  if (!(price->fz_floor >= 0.0)) return fail(BMPC_ERR_INVALID, "fz_floor must be >= 0 and not NaN");
+  if (int rc = plant_opts(plant, o); rc != BMPC_OK) return rc;
+  if (!ground)
+    for (int i = RO_GROUND; i < RO_REDUCED; ++i)
+      if (slots.s[i].p) return fail(BMPC_ERR_INVALID, "first_slip, slip_periods, unloaded_periods and mu_demand need a ground");
+  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
+  if (!x_fb || !foot || !contact || !controls) return fail(BMPC_ERR_INVALID, "x_fb, foot, contact and controls must be non-null");
+  if (!out) return fail(BMPC_ERR_INVALID, "null bmpc_rollout_out");
+  bool any_out = false;
+  for (const OutSlot& s : slots.s) any_out = any_out || s.p;
+  if (!any_out) return fail(BMPC_ERR_INVALID, "bmpc_rollout_out: at least one output must be non-null");
+  return check_batch(h, B);
+}
+
+// The launches, on device-addressable arrays; d: the slots of bmpc_rollout_out in its order.  The reductions read scores and
+// weights on the device: where the caller wants neither array they live in the handle's `samples` scratch, as for
+// bmpc_evaluate_samples (a call that has to grow it is not asynchronous).
+static int rollout_launch(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact, const float* x_cmd,
+                          const float* x_ref, const float* push, const float* controls, const bmpc_plant& o,
+                          const bmpc_plant_body* body, const bmpc_plant_ground* ground, const bmpc_rollout_price& price,
+                          void* const* d, hipStream_t st) {
+  const size_t n = (size_t)B * (size_t)price.S;
+  bool reduce = false;
+  for (int i = RO_REDUCED; i < N_RO; ++i) reduce = reduce || d[i];
+  double *score = (double*)d[RO_SCORE], *weights = (double*)d[RO_WEIGHTS];
+  const size_t need = (reduce && !score ? n : 0) + (reduce && !weights ? n : 0);
+  if (need) {
+    HIP_TRY(h->samples.ensure(need));
+    if (!score) score = h->samples.p;
+    if (!weights) weights = h->samples.p + (need - n);
+  }
+  const bmpc_params& p = h->params;
+  bmpc::RolloutCost C;
+  for (int i = 0; i < 12; ++i) { C.Q[i] = p.Q[i]; C.R[i] = p.R[i]; C.x_cmd[i] = p.x_cmd[i]; }
+  const bool bd = has_body(body);
+  const bmpc::RolloutIn in = {x_fb, foot, contact, x_cmd, x_ref, push, controls, bd ? body->m : nullptr, bd ? body->I : nullptr,
+                              bd ? body->g : nullptr, ground ? ground->mu : nullptr, p.mu, ground ? 1 : 0, o.move_feet != 0 ? 1 : 0,
+                              o.push_from, o.push_steps};
+  const bmpc::RolloutPrice pr = {price.tilt_max, price.z_min, price.fz_floor, price.w_fall, price.w_slip, price.w_unloaded};
+  const bmpc::RolloutOut out = {(double*)d[0], score, (float*)d[2], (float*)d[3], (float*)d[4], (int32_t*)d[5], (float*)d[6],
+                                (float*)d[7], (int32_t*)d[8], (int32_t*)d[9], (int32_t*)d[10], (float*)d[11]};
+  const size_t blocks = (n + bmpc::ROLLOUT_NT - 1) / bmpc::ROLLOUT_NT;       // (at most 2^24: B, S <= 65536)
+  hipLaunchKernelGGL(bmpc::plant_rollout_samples_kernel, dim3((unsigned)blocks), dim3(bmpc::ROLLOUT_NT), 0, st, plant_params(h),
+                     bmpc::plant_scheme(p.dt, o.integrator, o.substeps), C, in, pr, out, B, (int)price.S);
+  HIP_TRY(hipGetLastError());
+  if (reduce) {
+    hipLaunchKernelGGL(bmpc::sample_reduce_kernel, dim3((unsigned)B), dim3(bmpc::REDUCE_NT), 0, st, (int)p.h, (int)price.S,
+                       price.temperature, (const double*)score, controls,
+                       bmpc::ReduceOut{(int32_t*)d[12], (int32_t*)d[13], weights, (double*)d[15], (double*)d[16]});
+    HIP_TRY(hipGetLastError());
+  }
+  return BMPC_OK;
+}
+
+int bmpc_plant_rollout_samples_device(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
+                                      const float* x_cmd, const float* x_ref, const float* push, const float* controls,
+                                      const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                                      const bmpc_rollout_price* price, const bmpc_rollout_out* out, void* stream) {
+  const OutSlots<N_RO> slots = rollout_slots(out, price);
+  bmpc_plant o;
+  if (int rc = rollout_check(h, B, x_fb, foot, contact, controls, plant, ground, price, out, slots, &o); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  void* d[N_RO];
+  for (int i = 0; i < N_RO; ++i) d[i] = slots.s[i].p;
+  return rollout_launch(h, B, x_fb, foot, contact, x_cmd, x_ref, push, controls, o, body, ground, *price, d, pick_stream(h, stream));
+}
+
+// (staging: one block of the handle for the inputs and one for the wanted outputs, every array on an 8-byte boundary)
+int bmpc_plant_rollout_samples(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
+                               const float* x_cmd, const float* x_ref, const float* push, const float* controls,
+                               const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                               const bmpc_rollout_price* price, const bmpc_rollout_out* out) {
+  const OutSlots<N_RO> slots = rollout_slots(out, price);
+  bmpc_plant o;
+  if (int rc = rollout_check(h, B, x_fb, foot, contact, controls, plant, ground, price, out, slots, &o); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t n = (size_t)B, H = (size_t)h->dev.h, S = (size_t)price->S;
+  constexpr int N_RI = 11;
+  const void* src[N_RI] = {x_fb, foot, contact, x_cmd, x_ref, push, controls, body ? body->m : nullptr, body ? body->I : nullptr,
+                           body ? body->g : nullptr, ground ? ground->mu : nullptr};
+  const size_t in_bytes[N_RI] = {n * 48, n * 24, n * H * 2, n * 48, n * H * 48, n * 24, n * S * H * 48, n * 8, n * 72, n * 8, n * 16};
+  size_t in_off[N_RI], out_off[N_RO], out_bytes[N_RO], tot = 0;              // offsets and totals in doubles
+  for (int i = 0; i < N_RI; ++i) { in_off[i] = tot; tot += src[i] ? (in_bytes[i] + 7) / 8 : 0; }
+  HIP_TRY(h->rollout_in.ensure(tot));
+  hipStream_t st = h->stream;
+  const void* din[N_RI];
+  for (int i = 0; i < N_RI; ++i) {
+    din[i] = src[i] ? h->rollout_in.p + in_off[i] : nullptr;
+    if (src[i]) HIP_TRY(hipMemcpyAsync(h->rollout_in.p + in_off[i], src[i], in_bytes[i], hipMemcpyHostToDevice, st));
+  }
+  tot = 0;
+  for (int i = 0; i < N_RO; ++i) {
+    out_bytes[i] = slots.s[i].p ? n * slots.s[i].w.bytes(H) : 0;
+    out_off[i] = tot;
+    tot += (out_bytes[i] + 7) / 8;
+  }
+  HIP_TRY(h->rollout_out.ensure(tot));
+  void* d[N_RO];
+  for (int i = 0; i < N_RO; ++i) d[i] = slots.s[i].p ? h->rollout_out.p + out_off[i] : nullptr;
+  const bmpc_plant_body d_body = {(const double*)din[7], (const double*)din[8], (const double*)din[9]};
+  const bmpc_plant_ground d_ground = {(const double*)din[10]};
+  if (int rc = rollout_launch(h, B, (const float*)din[0], (const float*)din[1], (const uint8_t*)din[2], (const float*)din[3],
+                              (const float*)din[4], (const float*)din[5], (const float*)din[6], o, body ? &d_body : nullptr,
+                              ground ? &d_ground : nullptr, *price, d, st);
+      rc != BMPC_OK)
+    return rc;
+  for (int i = 0; i < N_RO; ++i)
+    if (slots.s[i].p) HIP_TRY(hipMemcpyAsync(slots.s[i].p, d[i], out_bytes[i], hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return BMPC_OK;
 }
 
 int bmpc_set_dispatch_order(bmpc_handle h, const int32_t* order_dev, int longest_first_rollouts) {

@@ -768,6 +768,92 @@ int bmpc_simulate_ground_device(bmpc_handle h, int B, int steps, const bmpc_plan
                                 float* foot_traj, int32_t* iters_traj, int32_t* status_any, const bmpc_sim_outcome* outcome,
                                 const bmpc_ground_out* gout, void* stream);
 
+/*
+ * S candidate plans per instance rolled out on the plant (added under ABI 13 like the entries above: detect them by the symbol).
+ * bmpc_evaluate_samples* scores S whole plans per instance through the controller's linearised model; the plant entries above
+ * integrate the rigid body for one control per instance and period.  These entries ask the rigid body what it makes of each of the
+ * S whole plans: nonlinear predictive sampling / MPPI next to the QP solver, a check of a solver's plan against the body before it is
+ * applied, and the model gap per plan (this cost minus bmpc_evaluate_samples' cost on the same reference).  One launch, one thread
+ * per plan, nothing replicated; max_batch bounds B, not B S.  Inputs, for B instances:
+ *   x_fb [B][12], foot [B][6], contact [B][h][2] (row k holds over period k), controls [B][S][h][12] fp32 (plan s of instance b);
+ *   x_cmd [B][12] or NULL (the handle's), x_ref [B][h][12] or NULL (generated), push [B][6] or NULL;
+ *   plant   integrator, substeps, move_feet, push_from, push_steps (NULL: the default);  body, ground  as above, each NULL as above
+ *   price   S, the thresholds of the fall outcome, the floor of the demand, the prices of the score and the temperature (below)
+ * Per period k = 0 .. h - 1 of plan (b, s):  u = controls[b][s][k];  with a ground, u_applied = what the ground transmits of u under
+ * contact[b][k] and mu[b] (the rule above), else u_applied = u;  the wrench is push[b] while push_from <= k < push_from + push_steps;
+ * the plant integrates the instance's body over the period and the new state is rounded to fp32 and STORED.  Period k + 1 starts
+ * from the stored state and EVERY output refers to it, so a roll-out is exactly the chain of bmpc_plant_step_ground_device calls a
+ * caller could make period by period.
+ *   cost    sum_k sum_i Q_i (x_k,i - xr_k,i)^2 + R_i u_k,i^2, i = 0 .. 11, in fp64 in that order: x_k the state stored after period k,
+ *           widened; u_k the COMMANDED control (as bmpc_evaluate* counts it, whatever the ground passed on); xr_k = x_ref[b][k] where
+ *           supplied, else generated as the solve generates it (REF:61-70; row 0 is x_fb).  With generated references this cost and
+ *           bmpc_evaluate_samples' cost are the same functional of two models.
+ *   landing by the TABLE: with move_feet != 0 and k + 1 < h, leg g lands if contact[b][k][g] == 0 and contact[b][k + 1][g] == 1; its
+ *           foothold becomes the swing controller's target (REF:428-435, the formula of bmpc_simulate_device) at the state stored
+ *           after period k, rounded to fp32; every other foothold stays
+ *   score   cost + w_fall [first_fall >= 0] + w_slip (slip_periods[0] + slip_periods[1])
+ *                + w_unloaded (unloaded_periods[0] + unloaded_periods[1]), added in that order
+ * Per-sample outputs, each optional: cost, score [B][S] fp64;  x_end [B][S][12], foot_end [B][S][6] (after the last landing),
+ * x_traj [B][S][h][12] fp32;  first_fall [B][S] int32, max_tilt, min_z [B][S] fp32 (bmpc_sim_outcome's rules over the h periods);
+ * first_slip [B][S], slip_periods [B][S][2], unloaded_periods [B][S][2] int32, mu_demand [B][S] fp32 (bmpc_ground_out's rules; they
+ * need a ground).  Per-instance reductions, each optional: best, n_valid, weights, u_mean, ess exactly as in bmpc_samples_out, from
+ * these scores and the commanded controls (the same kernel behind the first on the same stream; scores or weights the caller did
+ * not ask for live in the handle's scratch, with the rules stated there).
+ * A sample's values depend on nothing but its instance's inputs and its own controls: not on B, S, b or s.  A non-finite control
+ * entry of sample s at period k, or a plant step that goes bad there (|cos pitch| < 2^-22 at a stage), makes that sample's state
+ * NaN from period k on: its cost and score are NaN and its first_fall is k; no other sample is touched.  A bad INSTANCE makes every
+ * sample of it so: a non-finite x_fb or foot entry, a bad body, a mu that is NaN or negative (period 0); a non-finite push (the
+ * first period it acts in) or reference entry (the period of its row).
+ * Not modelled, as for the ground: a slipping foot does not slide, moments have no limit, static and kinetic friction are one
+ * number, the floor is flat at z = 0.  Bodies are per instance, not per sample; no noise is generated.
+ *   bmpc_plant_rollout_samples_device   DEVICE pointers (members of body, ground and out included), asynchronous on `stream`
+ *                                       (same rules as bmpc_evaluate_samples_device)
+ *   bmpc_plant_rollout_samples          HOST pointers, synchronous (staged through the handle's own stream)
+ * Checked before a device is touched, each BMPC_ERR_INVALID, in this order: `price` NULL, S outside [1, 65536], a price that is NaN,
+ * negative or infinite, a temperature that is NaN or <= 0, a NaN threshold, fz_floor NaN or negative; the plant block as for
+ * bmpc_simulate_device; first_slip, slip_periods, unloaded_periods or mu_demand wanted without a ground.  Then: a NULL handle, x_fb,
+ * foot, contact, controls or `out`; all outputs NULL; B outside [0, max_batch].  B = 0 succeeds.
+ * The handle's parameter block is read (bmpc_set_params takes effect) and none of its per-solve state is touched:
+ * bmpc_last_kernel_ms keeps reporting the last SOLVE.
+ */
+typedef struct bmpc_rollout_price {
+  int32_t S;                  /* samples per instance, 1 .. 65536 */
+  int32_t reserved0;
+  double  w_fall;             /* finite, >= 0: price of having fallen */
+  double  w_slip;             /* ... of each period a leg slipped */
+  double  w_unloaded;         /* ... of each period a stance leg was unloaded */
+  double  temperature;        /* > 0, +inf allowed (uniform weights) */
+  double  tilt_max, z_min;    /* fall thresholds as in bmpc_sim_outcome: not NaN; +inf / -inf switch one off */
+  double  fz_floor;           /* as in bmpc_ground_out: >= 0, not NaN */
+} bmpc_rollout_price;
+typedef struct bmpc_rollout_out {     /* each NULL = not wanted; at least one non-NULL */
+  double*  cost;              /* [B][S]        */
+  double*  score;             /* [B][S]        */
+  float*   x_end;             /* [B][S][12]    */
+  float*   foot_end;          /* [B][S][6]     */
+  float*   x_traj;            /* [B][S][h][12] */
+  int32_t* first_fall;        /* [B][S]        */
+  float*   max_tilt;          /* [B][S]        */
+  float*   min_z;             /* [B][S]        */
+  int32_t* first_slip;        /* [B][S]     (needs a ground, like the three below) */
+  int32_t* slip_periods;      /* [B][S][2]     */
+  int32_t* unloaded_periods;  /* [B][S][2]     */
+  float*   mu_demand;         /* [B][S]        */
+  int32_t* best;              /* [B]           */
+  int32_t* n_valid;           /* [B]           */
+  double*  weights;           /* [B][S]        */
+  double*  u_mean;            /* [B][h][12]    */
+  double*  ess;               /* [B]           */
+} bmpc_rollout_out;
+int bmpc_plant_rollout_samples_device(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
+                                      const float* x_cmd, const float* x_ref, const float* push, const float* controls,
+                                      const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                                      const bmpc_rollout_price* price, const bmpc_rollout_out* out, void* stream);
+int bmpc_plant_rollout_samples(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
+                               const float* x_cmd, const float* x_ref, const float* push, const float* controls,
+                               const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                               const bmpc_rollout_price* price, const bmpc_rollout_out* out);
+
 /* Diagnostics: when device_buf (DEVICE pointer, [max_batch][16] int64) is non-NULL every later solve
  * writes per-instance shader-clock stamps {setup, block algebra, dense sweeps, total, iters,
  * factorisations, -, -, iteration phases P0..P5, stop test + adaptation, -}; NULL switches it off
