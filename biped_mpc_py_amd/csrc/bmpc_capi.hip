@@ -21,6 +21,7 @@
 
 #include "bmpc.h"
 #include "bmpc_host_params.hpp"
+#include "bmpc_host_staging.hpp"
 
 namespace {
 
@@ -226,20 +227,14 @@ struct bmpc_handle_s {
   hipEvent_t cev_in = nullptr;      // the I/O block's inputs have arrived
   int io_gen = 0;                   // moves with every bmpc_host_io call (bmpc_host_io_generation)
   struct IoLayout : PackedLayout { int B = 0; } io;
-  DevBuf<char> stage[N_IN];         // host inputs on the device, one buffer per row of IN (stage_inputs, the low-level host entries)
-  DevBuf<float> controls;           // host controls of the evaluation family; what an assembly launch stores
-  DevBuf<double> eval_out;          // results of bmpc_evaluate (host pointers) on their way back
-  DevBuf<double> samples;           // bmpc_evaluate_samples*: scores / weights the reductions need and the caller did not ask for
+  // The staging of every other host-pointer entry.  A synchronous host entry is its _device twin between a stage and a fetch:
+  // all host inputs of the call are laid out in ONE block, host_in, all wanted outputs and the scratch of the call in ONE other,
+  // host_out (stage / carve / fetch below); the twin runs on the handle's own stream on pointers into them, the outputs are
+  // copied back and the stream is synchronised.  The entries are synchronous, so no two of them use the blocks at once.  No
+  // _device entry touches either: that keeps those asynchronous and leaves the handle alone.
+  DevBuf<char> host_in, host_out;
+  DevBuf<double> samples;           // sample reductions, either entry: scores / weights they need and the caller did not ask for
   DevBuf<int32_t> status;           // the rescue pass's, where the caller asks for none
-  DevBuf<double> dbg;
-  DevBuf<float> ll_q, ll_qd, ll_pf, ll_u0, ll_tau;
-  DevBuf<double> ll_t;
-  DevBuf<uint8_t> ll_c0;
-  DevBuf<double> body_m, body_I, body_g;   // bmpc_plant_step_body: the host body on the device
-  DevBuf<double> ground_mu;                // bmpc_plant_step_ground: the host ground on the device, and what it records on its way back
-  DevBuf<float> ground_ua;
-  DevBuf<uint8_t> ground_fl;
-  DevBuf<double> rollout_in, rollout_out;  // bmpc_plant_rollout_samples: the host arrays on the device, and the results on their way back
   long long* prof_dev = nullptr;   // optional cycle-stamp buffer (bmpc_debug_set_profile)
   // receding-horizon warm start (bmpc_set_warm_start): solver state of the last batch, kept on the device
   DevBuf<double> warm;
@@ -511,40 +506,89 @@ int solve_host(bmpc_handle h, int B, const bmpc_inputs& in, T* controls, T* stat
   return BMPC_OK;
 }
 
-// Host array `src` of `count` elements onto the device: the handle's buffer made large enough, the copy queued on the handle's
-// own stream; *dev: the copy, or null where src is.
-template <typename T, typename U>
-int upload(bmpc_handle h, DevBuf<T>& buf, const U* src, size_t count, const U** dev) {
-  *dev = nullptr;
-  if (!src) return BMPC_OK;
-  HIP_TRY(buf.ensure(count * sizeof(U) / sizeof(T)));
-  HIP_TRY(hipMemcpyAsync(buf.p, src, count * sizeof(U), hipMemcpyHostToDevice, h->stream));
-  *dev = reinterpret_cast<const U*>(buf.p);
+// ---- the synchronous host entries (the rule: bmpc_handle_s).  A further one is a table of rows and about ten lines.
+
+// One array of such a call: the caller's host array (null: the row is absent, it takes no room and its device pointer is null)
+// and its width.  An output row with `keep` set is laid out whatever p says: what the twin forms whether or not the caller wants
+// it back, and, with p null, scratch that is not copied back.
+struct InSlot { const void* p; Width w; };
+struct OutSlot { void* p; Width w; bool keep = false; };
+template <size_t N> struct OutSlots { OutSlot s[N]; };
+
+// widths of the low-level and plant entries' arrays that no table above holds
+constexpr Width W_JOINTS = {10, 0, 4}, W_FEET = {6, 0, 4}, W_WRENCH = {6, 0, 4}, W_U0 = {12, 0, 4}, W_CONTACT0 = {2, 0, 1},
+                W_FLAGS = {1, 0, 1}, W_T = {1, 0, 8}, W_MASS = {1, 0, 8}, W_INERTIA = {9, 0, 8}, W_GRAVITY = {1, 0, 8},
+                W_GROUND_MU = {2, 0, 8};
+// the f32 controls of `plans` plans per instance; a row of IN as the fp64 view an assembly launch stores
+constexpr Width controls_width(size_t plans = 1) { return {0, OUT[O_U].w.per_step * plans, sizeof(float)}; }
+constexpr Width f64_view(const Field& f) { return {f.w.fixed, f.w.per_step, sizeof(double)}; }
+
+// the rows of a block on the device, in table order: pointer (null: absent) and bytes of each, and the bytes of the block
+template <size_t N>
+struct Slices {
+  void* d[N];
+  size_t bytes[N], total;
+  template <typename T> T* at(size_t i) const { return static_cast<T*>(d[i]); }
+};
+
+// `rows` of B instances laid out in `block` (stage_layout of bmpc_host_staging.hpp), the block made large enough
+inline bool wanted(const InSlot& s) { return s.p; }
+inline bool wanted(const OutSlot& s) { return s.p || s.keep; }
+template <size_t N, typename Slot>
+int lay_out(bmpc_handle h, DevBuf<char>& block, int B, const Slot (&rows)[N], Slices<N>* L) {
+  StageRow r[N]; size_t off[N];
+  for (size_t i = 0; i < N; ++i) r[i] = {wanted(rows[i]), (size_t)B * rows[i].w.bytes((size_t)h->dev.h)};
+  L->total = stage_layout(r, N, off);
+  HIP_TRY(block.ensure(L->total));
+  for (size_t i = 0; i < N; ++i) { L->bytes[i] = r[i].bytes; L->d[i] = r[i].present ? block.p + off[i] : nullptr; }
   return BMPC_OK;
 }
 
-// The inputs of a solve, host arrays, onto the device through the handle's staging buffers (the synchronous host entries of the
-// evaluation family and bmpc_debug_assemble_inputs).  `controls`: host controls to stage with them, or null (the scratch array is
-// sized either way: the assembly launch stores there), `plans` of them per instance.  `din`: the descriptor of the copies.
-int stage_inputs(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, bmpc_inputs* din, size_t plans = 1) {
-  const size_t n = (size_t)B, H = (size_t)h->dev.h, nu = n * plans * OUT[O_U].w.count(H);
-  HIP_TRY(h->controls.ensure(nu));
-  for (int i = 0; i < N_IN; ++i) {
-    const char* d;
-    if (int rc = upload(h, h->stage[i], static_cast<const char*>(get_ptr(&in, IN[i].member)), n * IN[i].w.bytes(H), &d); rc != BMPC_OK) return rc;
-    set_ptr(din, IN[i].member, d);
-  }
-  if (controls) HIP_TRY(hipMemcpyAsync(h->controls.p, controls, nu * sizeof(float), hipMemcpyHostToDevice, h->stream));
+// stage: the host inputs of a call into host_in, one copy per present row queued on the handle's own stream
+template <size_t N>
+int stage(bmpc_handle h, int B, const InSlot (&in)[N], Slices<N>* L) {
+  if (int rc = lay_out(h, h->host_in, B, in, L); rc != BMPC_OK) return rc;
+  for (size_t i = 0; i < N; ++i)
+    if (in[i].p) HIP_TRY(hipMemcpyAsync(L->d[i], in[i].p, L->bytes[i], hipMemcpyHostToDevice, h->stream));
+  return BMPC_OK;
+}
+
+// carve: the wanted outputs and the scratch of a call out of host_out
+template <size_t N>
+int carve(bmpc_handle h, int B, const OutSlot (&out)[N], Slices<N>* L) { return lay_out(h, h->host_out, B, out, L); }
+
+// (both, for the entries that have nothing to do in between)
+template <size_t NI, size_t NO>
+int stage(bmpc_handle h, int B, const InSlot (&in)[NI], Slices<NI>* d, const OutSlot (&out)[NO], Slices<NO>* o) {
+  const int rc = stage(h, B, in, d);
+  return rc != BMPC_OK ? rc : carve(h, B, out, o);
+}
+
+// fetch: one copy back per wanted output, then the call waits for its stream
+template <size_t N>
+int fetch(bmpc_handle h, const OutSlot (&out)[N], const Slices<N>& L) {
+  for (size_t i = 0; i < N; ++i)
+    if (out[i].p) HIP_TRY(hipMemcpyAsync(out[i].p, L.d[i], L.bytes[i], hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return BMPC_OK;
+}
+
+// The inputs of a solve, host arrays, and `controls` (null: none) of `plans` plans per instance behind them, staged: *din the
+// descriptor of the copies, *dcontrols the controls' (the evaluation family's host entries and bmpc_debug_assemble_inputs).
+int stage_inputs(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, size_t plans, bmpc_inputs* din, const float** dcontrols) {
+  InSlot rows[N_IN + 1];
+  for (int i = 0; i < N_IN; ++i) rows[i] = {get_ptr(&in, IN[i].member), IN[i].w};
+  rows[N_IN] = {controls, controls_width(plans)};
+  Slices<N_IN + 1> L;
+  if (int rc = stage(h, B, rows, &L); rc != BMPC_OK) return rc;
+  for (int i = 0; i < N_IN; ++i) set_ptr(din, IN[i].member, L.d[i]);
+  *dcontrols = L.at<const float>(N_IN);
   return BMPC_OK;
 }
 
 // ---- the evaluation family: bmpc_evaluate, bmpc_evaluate_grad, bmpc_certify and their _device twins.  One launch each, nothing
 // of the handle's per-solve state involved.  The kernels differ (bmpc_evaluate.hip, bmpc_evaluate_grad.hip, bmpc_certify.hip);
 // the path around them is stated once here.  A further operation is a kernel, an EvalOp row, a slot table and two entries.
-
-// one member of an operation's output descriptor: the caller's pointer (null: not wanted) and the array's width
-struct OutSlot { void* p; Width w; };
-template <size_t N> struct OutSlots { OutSlot s[N]; };
 
 // what an operation takes besides the inputs and the controls: certify's act_tol, the sampling descriptor of evaluate_samples
 struct EvalArg { double act_tol = 0.0; const bmpc_samples* smp = nullptr; };
@@ -575,39 +619,51 @@ int launch_certify(bmpc_handle h, int B, const bmpc_inputs& in, const float* con
                                            bmpc::CertOut{(double*)o[0], (double*)o[1], (double*)o[2], (int32_t*)o[3], (int32_t*)o[4]});
 }
 
-// evaluate_samples: the per-sample kernel over B ceil(S / C) groups, C samples each (bmpc::eval_samples_per_group), then -- where a
-// reduced output is wanted -- the per-instance reductions behind it on the same stream.  The reductions read the scores and the
-// weights from the device: where the caller wants neither array, they live in the handle's scratch, grown on demand (a call
-// that has to grow it is not asynchronous: the old block is freed).  o: the slots of bmpc_samples_out, in its order.
-int launch_evaluate_samples(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const EvalArg& arg, void* const* o,
-                            hipStream_t st) {
-  const bmpc_samples& smp = *arg.smp;
-  const size_t n = (size_t)B * (size_t)smp.S;
-  const bool reduce = o[3] || o[4] || o[5] || o[6] || o[7];
-  double *score = (double*)o[2], *weights = (double*)o[5];
-  const size_t need = (score ? 0 : n) + (reduce && !weights ? n : 0);
-  if (need) {
-    HIP_TRY(h->samples.ensure(need));
-    if (!score) score = h->samples.p;
-    if (reduce && !weights) weights = h->samples.p + (need - n);
+// The tail both sampling operations share: `per_sample(score)`, the operation's own launch, then -- where one of the reduced
+// outputs r[0 .. 4] (best, n_valid, weights, u_mean, ess: the order of both descriptors) is wanted -- the per-instance reductions
+// behind it on the same stream.  The reductions read the scores and the weights from the device: where the caller wants
+// neither array they live in the handle's `samples` scratch, grown on demand (a call that has to grow it is not asynchronous:
+// the old block is freed).  `always_score`: the per-sample kernel stores its scores whether or not anything is reduced.
+template <typename PerSample>
+int launch_sampled(bmpc_handle h, int B, int S, double temperature, bool always_score, double* score, const float* controls,
+                   void* const* r, hipStream_t st, PerSample per_sample) {
+  const size_t n = (size_t)B * (size_t)S;
+  const bool reduce = r[0] || r[1] || r[2] || r[3] || r[4];
+  double* weights = (double*)r[2];
+  const bool own_score = (always_score || reduce) && !score, own_weights = reduce && !weights;
+  if (own_score || own_weights) {
+    HIP_TRY(h->samples.ensure(n * ((size_t)own_score + (size_t)own_weights)));
+    if (own_score) score = h->samples.p;
+    if (own_weights) weights = h->samples.p + (own_score ? n : 0);
   }
-  const int C = bmpc::eval_samples_per_group(B, smp.S);
-  const long long groups = (long long)B * (((long long)smp.S + C - 1) / C);
-  const long long blocks = (groups * bmpc::eval_lanes(h->params.h) + bmpc::EVAL_NT - 1) / bmpc::EVAL_NT;
-  if (blocks > 0x7fffffffLL) return fail(BMPC_ERR_INVALID, "B x S = %zu plans are more than one launch holds", n);
-  bmpc::SamplesPrice price;
-  for (int c = 0; c < 4; ++c) price.w[c] = smp.w_viol[c];
-  hipLaunchKernelGGL(bmpc::evaluate_samples_kernel, dim3((unsigned)blocks), dim3(bmpc::EVAL_NT), 0, st,
-                     bmpc::eval_params(h->params, h->dev.Iinv), B, (int)smp.S, C, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd, in.mu,
-                     in.x_ref, in.foot_ref, controls, price, bmpc::SamplesOut{(double*)o[0], (double*)o[1], score});
+  if (int rc = per_sample(score); rc != BMPC_OK) return rc;
   HIP_TRY(hipGetLastError());
   if (reduce) {
-    hipLaunchKernelGGL(bmpc::sample_reduce_kernel, dim3((unsigned)B), dim3(bmpc::REDUCE_NT), 0, st, (int)h->params.h, (int)smp.S,
-                       smp.temperature, (const double*)score, controls,
-                       bmpc::ReduceOut{(int32_t*)o[3], (int32_t*)o[4], weights, (double*)o[6], (double*)o[7]});
+    hipLaunchKernelGGL(bmpc::sample_reduce_kernel, dim3((unsigned)B), dim3(bmpc::REDUCE_NT), 0, st, (int)h->params.h, S, temperature,
+                       (const double*)score, controls, bmpc::ReduceOut{(int32_t*)r[0], (int32_t*)r[1], weights, (double*)r[3], (double*)r[4]});
     HIP_TRY(hipGetLastError());
   }
   return BMPC_OK;
+}
+
+// evaluate_samples: the per-sample kernel over B ceil(S / C) groups, C samples each (bmpc::eval_samples_per_group), and the
+// reductions.  o: the slots of bmpc_samples_out, in its order.
+int launch_evaluate_samples(bmpc_handle h, int B, const bmpc_inputs& in, const float* controls, const EvalArg& arg, void* const* o,
+                            hipStream_t st) {
+  const bmpc_samples& smp = *arg.smp;
+  return launch_sampled(h, B, (int)smp.S, smp.temperature, true, (double*)o[2], controls, o + 3, st, [&](double* score) {
+    const int C = bmpc::eval_samples_per_group(B, smp.S);
+    const long long groups = (long long)B * (((long long)smp.S + C - 1) / C);
+    const long long blocks = (groups * bmpc::eval_lanes(h->params.h) + bmpc::EVAL_NT - 1) / bmpc::EVAL_NT;
+    if (blocks > 0x7fffffffLL)
+      return fail(BMPC_ERR_INVALID, "B x S = %zu plans are more than one launch holds", (size_t)B * (size_t)smp.S);
+    bmpc::SamplesPrice price;
+    for (int c = 0; c < 4; ++c) price.w[c] = smp.w_viol[c];
+    hipLaunchKernelGGL(bmpc::evaluate_samples_kernel, dim3((unsigned)blocks), dim3(bmpc::EVAL_NT), 0, st,
+                       bmpc::eval_params(h->params, h->dev.Iinv), B, (int)smp.S, C, in.x_fb, in.foot, in.contact, in.phase, in.x_cmd,
+                       in.mu, in.x_ref, in.foot_ref, controls, price, bmpc::SamplesOut{(double*)o[0], (double*)o[1], score});
+    return (int)BMPC_OK;
+  });
 }
 
 const EvalOp EVALUATE = {"null bmpc_eval_out", "bmpc_eval_out: at least one of cost, objective, states, violation must be non-null",
@@ -642,15 +698,22 @@ OutSlots<8> slots_of(const bmpc_samples_out* out, const bmpc_samples* smp) {
            {o.weights, {S, 0, 8}}, {o.u_mean, {0, 12, 8}}, {o.ess, {1, 0, 8}}}};
 }
 
-// the sampling descriptor of bmpc_evaluate_samples*, checked before anything else of the call (as certify's act_tol is)
+// What both sampling descriptors (`name`: bmpc_samples, bmpc_rollout_price) hold alike, checked before anything else of the
+// call: S, the nw prices w -- `which` names them in the message, and may take the index of the offending one --, the temperature
+int check_sampling(const char* name, int S, const double* w, int nw, const char* which, double temperature) {
+  if (S < 1 || S > bmpc::SAMPLES_MAX) return fail(BMPC_ERR_INVALID, "%s: S = %d outside [1, %d]", name, S, bmpc::SAMPLES_MAX);
+  char what[64];
+  for (int c = 0; c < nw; ++c)
+    if (!(w[c] >= 0.0 && w[c] <= 1.7976931348623157e308)) {
+      std::snprintf(what, sizeof(what), which, c);
+      return fail(BMPC_ERR_INVALID, "%s: %s must be finite and >= 0", name, what);
+    }
+  if (!(temperature > 0.0)) return fail(BMPC_ERR_INVALID, "%s: temperature must be > 0 (+inf allowed)", name);
+  return BMPC_OK;
+}
 int check_samples(const bmpc_samples* smp) {
   if (!smp) return fail(BMPC_ERR_INVALID, "null bmpc_samples");
-  if (smp->S < 1 || smp->S > bmpc::SAMPLES_MAX) return fail(BMPC_ERR_INVALID, "bmpc_samples: S = %d outside [1, %d]", (int)smp->S, bmpc::SAMPLES_MAX);
-  for (int c = 0; c < 4; ++c)
-    if (!(smp->w_viol[c] >= 0.0 && smp->w_viol[c] <= 1.7976931348623157e308))
-      return fail(BMPC_ERR_INVALID, "bmpc_samples: w_viol[%d] must be finite and >= 0", c);
-  if (!(smp->temperature > 0.0)) return fail(BMPC_ERR_INVALID, "bmpc_samples: temperature must be > 0 (+inf allowed)");
-  return BMPC_OK;
+  return check_sampling("bmpc_samples", (int)smp->S, smp->w_viol, 4, "w_viol[%d]", smp->temperature);
 }
 
 // what every entry checks before a device is touched (and before the handle is read): an error code (< 0), BMPC_OK when there is
@@ -679,32 +742,19 @@ int eval_device(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, c
   return op.launch(h, B, *in, controls, arg, d, pick_stream(h, stream));
 }
 
-// the host entry: the wanted outputs are carved out of the handle's eval_out block (each on an 8-byte boundary), the inputs
-// staged, the kernel launched on the copies, the outputs copied back; synchronous on the handle's own stream
+// the host entry: the operation's launch between stage and fetch (controls of B * S plans where there is a sampling descriptor)
 template <size_t N>
 int eval_host(const EvalOp& op, bmpc_handle h, int B, const bmpc_inputs* in, const float* controls, const EvalArg& arg,
               const void* out, const OutSlots<N>& slots) {
   if (int rc = check_eval(op, h, B, in, controls, out, slots); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B, H = (size_t)h->dev.h;
-  size_t bytes[N], off[N], tot = 0;                       // off, tot in doubles
-  for (size_t i = 0; i < N; ++i) {
-    const OutSlot& s = slots.s[i];
-    bytes[i] = s.p ? n * s.w.bytes(H) : 0;
-    off[i] = tot;
-    tot += (bytes[i] + sizeof(double) - 1) / sizeof(double);
-  }
-  HIP_TRY(h->eval_out.ensure(tot));
+  Slices<N> o;
+  if (int rc = carve(h, B, slots.s, &o); rc != BMPC_OK) return rc;
   bmpc_inputs din;
-  if (int rc = stage_inputs(h, B, *in, controls, &din, arg.smp ? (size_t)arg.smp->S : 1); rc != BMPC_OK) return rc;
-  hipStream_t st = h->stream;
-  void* d[N];
-  for (size_t i = 0; i < N; ++i) d[i] = slots.s[i].p ? h->eval_out.p + off[i] : nullptr;
-  if (int rc = op.launch(h, B, din, h->controls.p, arg, d, st); rc != BMPC_OK) return rc;
-  for (size_t i = 0; i < N; ++i)
-    if (slots.s[i].p) HIP_TRY(hipMemcpyAsync(slots.s[i].p, d[i], bytes[i], hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return BMPC_OK;
+  const float* dcontrols;
+  if (int rc = stage_inputs(h, B, *in, controls, arg.smp ? (size_t)arg.smp->S : 1, &din, &dcontrols); rc != BMPC_OK) return rc;
+  if (int rc = op.launch(h, B, din, dcontrols, arg, o.d, h->stream); rc != BMPC_OK) return rc;
+  return fetch(h, slots.s, o);
 }
 
 }  // namespace
@@ -962,29 +1012,24 @@ int bmpc_debug_assemble_inputs(bmpc_handle h, int B, const bmpc_inputs* in, doub
   float dummy = 0;
   if (int rc = check_common(h, B, *in, &dummy); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B, H = (size_t)h->dev.h, NW = 6 * H;
-  // only what the caller asked for is formed: Gt alone is n (6h)^2 doubles (1.9 GB at B = 4096, h = 40), and the Gt / qt
-  // views exist on the dense family only (h <= 20) -- a caller that wants the references gets them at every horizon
+  const size_t NW = 6 * (size_t)h->dev.h;
+  // Gt and qt are formed only where the caller asked for them: Gt alone is n (6h)^2 doubles (1.9 GB at B = 4096, h = 40), and
+  // the Gt / qt views exist on the dense family only (h <= 20) -- a caller that wants the references gets them at every horizon
   if ((Gt || qt) && !dense_horizon(h->dev.h))
     return fail(BMPC_ERR_INVALID, "Gt / qt views exist for h <= 20 only (h=%d never forms them); pass NULL for both", h->dev.h);
-  const size_t o_xr = 0, o_fr = o_xr + n * H * 12, o_gt = o_fr + n * H * 6, o_qt = o_gt + (Gt ? n * NW * NW : 0),
-               tot = o_qt + (qt ? n * NW : 0);
-  HIP_TRY(h->dbg.ensure(tot));
-  hipStream_t st = h->stream;
-  HIP_TRY(hipMemsetAsync(h->dbg.p, 0, tot * sizeof(double), st));
-  bmpc_inputs din;
-  if (int rc = stage_inputs(h, B, *in, nullptr, &din); rc != BMPC_OK) return rc;
-  bmpc::DebugOut dbg = {h->dbg.p + o_xr, h->dbg.p + o_fr, Gt ? h->dbg.p + o_gt : nullptr, qt ? h->dbg.p + o_qt : nullptr, nullptr, 1};
+  // (the references are formed either way; the last row is the controls an assembly launch stores: scratch)
+  const OutSlot out[5] = {{x_ref, f64_view(IN[I_XREF]), true}, {foot_ref, f64_view(IN[I_FREF]), true}, {Gt, {NW * NW, 0, 8}},
+                          {qt, {NW, 0, 8}}, {nullptr, controls_width(), true}};
+  Slices<5> o;
+  if (int rc = carve(h, B, out, &o); rc != BMPC_OK) return rc;
+  HIP_TRY(hipMemsetAsync(h->host_out.p, 0, o.total, h->stream));
   SolveIO io;
-  io.in = din;
-  io.controls = h->controls.p;
-  if (int rc = launch(h, B, io, dbg, st, nullptr); rc != BMPC_OK) return rc;
-  if (x_ref) HIP_TRY(hipMemcpyAsync(x_ref, h->dbg.p + o_xr, n * H * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (foot_ref) HIP_TRY(hipMemcpyAsync(foot_ref, h->dbg.p + o_fr, n * H * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (Gt) HIP_TRY(hipMemcpyAsync(Gt, h->dbg.p + o_gt, n * NW * NW * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (qt) HIP_TRY(hipMemcpyAsync(qt, h->dbg.p + o_qt, n * NW * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return BMPC_OK;
+  const float* none;
+  if (int rc = stage_inputs(h, B, *in, nullptr, 1, &io.in, &none); rc != BMPC_OK) return rc;
+  io.controls = o.at<float>(4);
+  const bmpc::DebugOut dbg = {o.at<double>(0), o.at<double>(1), o.at<double>(2), o.at<double>(3), nullptr, 1};
+  if (int rc = launch(h, B, io, dbg, h->stream, nullptr); rc != BMPC_OK) return rc;
+  return fetch(h, out, o);
 }
 
 int bmpc_debug_assemble(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
@@ -1057,17 +1102,13 @@ int bmpc_foot_position_world_device(bmpc_handle h, int B, const float* x_fb, con
 int bmpc_foot_position_world(bmpc_handle h, int B, const float* x_fb, const float* q, float* pf_w) {
   if (int rc = check_batch(h, B); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B;
-  const float *d_x, *d_q;
-  int rc = upload(h, h->stage[I_XFB], x_fb, n * IN[I_XFB].w.count(0), &d_x);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_q, q, n * 10, &d_q);
-  if (rc != BMPC_OK) return rc;
-  HIP_TRY(h->ll_pf.ensure(n * 6));
-  rc = bmpc_foot_position_world_device(h, B, d_x, d_q, pf_w ? h->ll_pf.p : nullptr, h->stream);
-  if (rc != BMPC_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(pf_w, h->ll_pf.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return BMPC_OK;
+  const InSlot in[2] = {{x_fb, IN[I_XFB].w}, {q, W_JOINTS}};
+  const OutSlot out[1] = {{pf_w, W_FEET}};
+  Slices<2> d; Slices<1> o;
+  if (int rc = stage(h, B, in, &d, out, &o); rc != BMPC_OK) return rc;
+  // (a null array is an absent row and a null pointer: the twin refuses it)
+  const int rc = bmpc_foot_position_world_device(h, B, d.at<float>(0), d.at<float>(1), o.at<float>(0), h->stream);
+  return rc != BMPC_OK ? rc : fetch(h, out, o);
 }
 
 int bmpc_low_level_control_device(bmpc_handle h, int B, const float* x_fb, const double* t, const float* pf_w,
@@ -1087,23 +1128,13 @@ int bmpc_low_level_control(bmpc_handle h, int B, const float* x_fb, const double
                            const float* q, const float* qd, const uint8_t* contact0, const float* u0, float* tau) {
   if (int rc = check_batch(h, B); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B;
-  const float *d_x, *d_pf, *d_q, *d_qd, *d_u0;
-  const double* d_t; const uint8_t* d_c0;
-  int rc = upload(h, h->stage[I_XFB], x_fb, n * IN[I_XFB].w.count(0), &d_x);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_t, t, n, &d_t);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_pf, pf_w, n * 6, &d_pf);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_q, q, n * 10, &d_q);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_qd, qd, n * 10, &d_qd);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_c0, contact0, n * 2, &d_c0);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_u0, u0, n * 12, &d_u0);
-  if (rc != BMPC_OK) return rc;
-  HIP_TRY(h->ll_tau.ensure(n * 10));
-  rc = bmpc_low_level_control_device(h, B, d_x, d_t, d_pf, d_q, d_qd, d_c0, d_u0, tau ? h->ll_tau.p : nullptr, h->stream);
-  if (rc != BMPC_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(tau, h->ll_tau.p, n * 10 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return BMPC_OK;
+  const InSlot in[7] = {{x_fb, IN[I_XFB].w}, {t, W_T}, {pf_w, W_FEET}, {q, W_JOINTS}, {qd, W_JOINTS}, {contact0, W_CONTACT0}, {u0, W_U0}};
+  const OutSlot out[1] = {{tau, W_JOINTS}};
+  Slices<7> d; Slices<1> o;
+  if (int rc = stage(h, B, in, &d, out, &o); rc != BMPC_OK) return rc;
+  const int rc = bmpc_low_level_control_device(h, B, d.at<float>(0), d.at<double>(1), d.at<float>(2), d.at<float>(3), d.at<float>(4),
+                                             d.at<uint8_t>(5), d.at<float>(6), o.at<float>(0), h->stream);
+  return rc != BMPC_OK ? rc : fetch(h, out, o);
 }
 
 int bmpc_gait_default(bmpc_gait* g, int half) {
@@ -1144,19 +1175,12 @@ int bmpc_contact_sequence_device(bmpc_handle h, int B, const double* t, const bm
 int bmpc_contact_sequence(bmpc_handle h, int B, const double* t, const bmpc_gait* gait, int32_t* phase, uint8_t* contact) {
   if (int rc = check_batch(h, B); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B, H = (size_t)h->params.h;
-  const double* d_t;
-  if (int rc = upload(h, h->ll_t, t, n, &d_t); rc != BMPC_OK) return rc;
-  DevBuf<char>&d_phase = h->stage[I_PHASE], &d_contact = h->stage[I_CON];
-  HIP_TRY(d_phase.ensure(n * IN[I_PHASE].w.bytes(H)));
-  HIP_TRY(d_contact.ensure(n * IN[I_CON].w.bytes(H)));
-  int rc = bmpc_contact_sequence_device(h, B, d_t, gait, reinterpret_cast<int32_t*>(d_phase.p), reinterpret_cast<uint8_t*>(d_contact.p),
-                                        h->stream);
-  if (rc != BMPC_OK) return rc;
-  if (phase) HIP_TRY(hipMemcpyAsync(phase, d_phase.p, n * IN[I_PHASE].w.bytes(H), hipMemcpyDeviceToHost, h->stream));
-  if (contact) HIP_TRY(hipMemcpyAsync(contact, d_contact.p, n * IN[I_CON].w.bytes(H), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return BMPC_OK;
+  const InSlot in[1] = {{t, W_T}};
+  const OutSlot out[2] = {{phase, IN[I_PHASE].w, true}, {contact, IN[I_CON].w, true}};     // (both formed, either may be unwanted)
+  Slices<1> d; Slices<2> o;
+  if (int rc = stage(h, B, in, &d, out, &o); rc != BMPC_OK) return rc;
+  const int rc = bmpc_contact_sequence_device(h, B, d.at<double>(0), gait, o.at<int32_t>(0), o.at<uint8_t>(1), h->stream);
+  return rc != BMPC_OK ? rc : fetch(h, out, o);
 }
 
 int bmpc_set_warm_start(bmpc_handle h, int enable, int shift, double theta) {
@@ -1175,6 +1199,10 @@ int bmpc_reset_warm_start(bmpc_handle h) {
   h->warm_valid = false;
   return BMPC_OK;
 }
+
+// period s of a trajectory array of `per_period` elements a period (null: not recorded)
+extern "C++" template <typename T>
+static T* period_slice(T* traj, int s, size_t per_period) { return traj ? traj + (size_t)s * per_period : nullptr; }
 
 // The closed loop bmpc_rollout_device and bmpc_simulate_device share: per period  t -> (phase, contact)  ->  dispatch order (from the
 // second period on, where the roll-out orders its own: the instances that iterated longest last period go first)  ->  solve  ->
@@ -1225,8 +1253,7 @@ int bmpc_rollout_device(bmpc_handle h, int B, int steps, float* x_fb, const floa
   return closed_loop(h, B, steps, x_fb, foot, t, gait, x_cmd, mu, status_any, stream, [&](int s, hipStream_t st) {
     hipLaunchKernelGGL(bmpc::rollout_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, (int)h->dev.h, h->params.dt,
                        h->ro_states.p, h->ro_controls.p, h->ro_iters.p, h->ro_status.p, x_fb, t,
-                       u0_traj ? u0_traj + (size_t)s * n * 12 : nullptr, x_traj ? x_traj + (size_t)s * n * 12 : nullptr,
-                       iters_traj ? iters_traj + (size_t)s * n : nullptr, status_any);
+                       period_slice(u0_traj, s, n * 12), period_slice(x_traj, s, n * 12), period_slice(iters_traj, s, n), status_any);
   });
 }
 
@@ -1299,7 +1326,6 @@ static int plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, cons
 }
 
 // bmpc_plant_step, bmpc_plant_step_body and bmpc_plant_step_ground
-// (staging: the buffers of the low-level host entries -- ll_pf holds foot positions there too; ll_q the wrench, ll_tau the result)
 static int plant_step_host(bmpc_handle h, int B, const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
                            const float* x_fb, const float* u0, const float* foot, const uint8_t* contact0, const float* wrench,
                            float* x_next, float* u_applied, uint8_t* flags) {
@@ -1309,32 +1335,17 @@ static int plant_step_host(bmpc_handle h, int B, const bmpc_plant* plant, const 
   if (int rc = check_batch(h, B); rc <= 0) return rc;
   if (!x_fb || !u0 || !foot || !contact0 || !x_next) return fail(BMPC_ERR_INVALID, "x_fb, u0, foot, contact0 and x_next must be non-null");
   HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B;
-  const float *d_x, *d_u0, *d_foot, *d_w;
-  const uint8_t* d_c0;
-  bmpc_plant_body d_body = {nullptr, nullptr, nullptr};
-  bmpc_plant_ground d_ground = {nullptr};
-  int rc = upload(h, h->stage[I_XFB], x_fb, n * IN[I_XFB].w.count(0), &d_x);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_u0, u0, n * 12, &d_u0);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_pf, foot, n * 6, &d_foot);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_c0, contact0, n * 2, &d_c0);
-  if (rc == BMPC_OK) rc = upload(h, h->ll_q, wrench, n * 6, &d_w);
-  if (rc == BMPC_OK && body) rc = upload(h, h->body_m, body->m, n, &d_body.m);
-  if (rc == BMPC_OK && body) rc = upload(h, h->body_I, body->I, n * 9, &d_body.I);
-  if (rc == BMPC_OK && body) rc = upload(h, h->body_g, body->g, n, &d_body.g);
-  if (rc == BMPC_OK && ground) rc = upload(h, h->ground_mu, ground->mu, n * 2, &d_ground.mu);
-  if (rc != BMPC_OK) return rc;
-  HIP_TRY(h->ll_tau.ensure(n * 12));
-  if (u_applied) HIP_TRY(h->ground_ua.ensure(n * 12));
-  if (flags) HIP_TRY(h->ground_fl.ensure(n));
-  rc = plant_step_device(h, B, &o, &d_body, ground ? &d_ground : nullptr, d_x, d_u0, d_foot, d_c0, d_w, h->ll_tau.p,
-                         u_applied ? h->ground_ua.p : nullptr, flags ? h->ground_fl.p : nullptr, h->stream);
-  if (rc != BMPC_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(x_next, h->ll_tau.p, n * 12 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (u_applied) HIP_TRY(hipMemcpyAsync(u_applied, h->ground_ua.p, n * 12 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (flags) HIP_TRY(hipMemcpyAsync(flags, h->ground_fl.p, n, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return BMPC_OK;
+  const InSlot in[9] = {{x_fb, IN[I_XFB].w}, {u0, W_U0}, {foot, W_FEET}, {contact0, W_CONTACT0}, {wrench, W_WRENCH},
+                        {body ? body->m : nullptr, W_MASS}, {body ? body->I : nullptr, W_INERTIA}, {body ? body->g : nullptr, W_GRAVITY},
+                        {ground ? ground->mu : nullptr, W_GROUND_MU}};
+  const OutSlot out[3] = {{x_next, IN[I_XFB].w}, {u_applied, W_U0}, {flags, W_FLAGS}};
+  Slices<9> d; Slices<3> r;
+  if (int rc = stage(h, B, in, &d, out, &r); rc != BMPC_OK) return rc;
+  const bmpc_plant_body d_body = {d.at<double>(5), d.at<double>(6), d.at<double>(7)};
+  const bmpc_plant_ground d_ground = {d.at<double>(8)};
+  const int rc = plant_step_device(h, B, &o, &d_body, ground ? &d_ground : nullptr, d.at<float>(0), d.at<float>(1), d.at<float>(2),
+                                 d.at<uint8_t>(3), d.at<float>(4), r.at<float>(0), r.at<float>(1), r.at<uint8_t>(2), h->stream);
+  return rc != BMPC_OK ? rc : fetch(h, out, r);
 }
 
 int bmpc_plant_step_device(bmpc_handle h, int B, const bmpc_plant* plant, const float* x_fb, const float* u0, const float* foot,
@@ -1419,16 +1430,15 @@ static int simulate(bmpc_handle h, int B, int steps, const bmpc_plant* plant, co
   return closed_loop(h, B, steps, x_fb, foot, t, gait, x_cmd, mu, status_any, stream, [&](int s, hipStream_t st) {
     const bool push_on = push && s >= o.push_from && s - o.push_from < o.push_steps;
     const float* w = push_on ? push : nullptr;
-    float *u0_s = u0_traj ? u0_traj + (size_t)s * n * 12 : nullptr, *x_s = x_traj ? x_traj + (size_t)s * n * 12 : nullptr,
-          *foot_s = foot_traj ? foot_traj + (size_t)s * n * 6 : nullptr;
-    int32_t* iters_s = iters_traj ? iters_traj + (size_t)s * n : nullptr;
+    float *u0_s = period_slice(u0_traj, s, n * 12), *x_s = period_slice(x_traj, s, n * 12), *foot_s = period_slice(foot_traj, s, n * 6);
+    int32_t* iters_s = period_slice(iters_traj, s, n);
     if (ground) {
       // (the reduction first: it reads the solve's outputs, which the feedback step leaves alone, and nothing that step writes)
       if (has_ground_sum(gout))
         hipLaunchKernelGGL(bmpc::ground_reduce_kernel, dim3((B + 255) / 256), dim3(256), 0, st, ground->mu, h->params.mu, R, s, B,
                            (int)h->dev.h, h->ro_controls.p, h->ro_contact.p);
-      const bmpc::PlantGround Gr = {ground->mu, h->params.mu, gout && gout->u_applied ? gout->u_applied + (size_t)s * n * 12 : nullptr,
-                                    gout && gout->flags ? gout->flags + (size_t)s * n : nullptr};
+      const bmpc::PlantGround Gr = {ground->mu, h->params.mu, period_slice(gout ? gout->u_applied : nullptr, s, n * 12),
+                                    period_slice(gout ? gout->flags : nullptr, s, n)};
       hipLaunchKernelGGL(bmpc::simulate_ground_feedback_kernel, dim3((B + 255) / 256), dim3(256), 0, st, P, Bd, O, Gr, s, S, PG, B,
                          h->ro_controls.p, h->ro_contact.p, h->ro_iters.p, h->ro_status.p, w, x_cmd, x_fb, foot, t, u0_s, x_s, foot_s,
                          iters_s, status_any);
@@ -1471,7 +1481,7 @@ int bmpc_simulate_ground_device(bmpc_handle h, int B, int steps, const bmpc_plan
 
 // the outputs of bmpc_rollout_out in its member order: elements per instance (S: per sample) and bytes per element; a null
 // descriptor gives all-null slots.  Slots 8 .. 11 need a ground, 12 .. 16 are sample_reduce_kernel's.
-constexpr int RO_SCORE = 1, RO_GROUND = 8, RO_REDUCED = 12, RO_WEIGHTS = 14, N_RO = 17;
+constexpr int RO_SCORE = 1, RO_GROUND = 8, RO_REDUCED = 12, N_RO = 17;
 static OutSlots<N_RO> rollout_slots(const bmpc_rollout_out* out, const bmpc_rollout_price* price) {
   const bmpc_rollout_out o = out ? *out : bmpc_rollout_out{};
   const size_t S = price && price->S >= 1 && price->S <= bmpc::SAMPLES_MAX ? (size_t)price->S : 1;
@@ -1486,13 +1496,9 @@ static int rollout_check(bmpc_handle h, int B, const float* x_fb, const float* f
                          const bmpc_plant* plant, const bmpc_plant_ground* ground, const bmpc_rollout_price* price,
                          const bmpc_rollout_out* out, const OutSlots<N_RO>& slots, bmpc_plant* o) {
   if (!price) return fail(BMPC_ERR_INVALID, "null bmpc_rollout_price");
-  if (price->S < 1 || price->S > bmpc::SAMPLES_MAX)
-    return fail(BMPC_ERR_INVALID, "bmpc_rollout_price: S = %d outside [1, %d]", (int)price->S, bmpc::SAMPLES_MAX);
   const double w[3] = {price->w_fall, price->w_slip, price->w_unloaded};
-  for (int c = 0; c < 3; ++c)
-    if (!(w[c] >= 0.0 && w[c] <= 1.7976931348623157e308))
-      return fail(BMPC_ERR_INVALID, "bmpc_rollout_price: w_fall, w_slip and w_unloaded must be finite and >= 0");
-  if (!(price->temperature > 0.0)) return fail(BMPC_ERR_INVALID, "bmpc_rollout_price: temperature must be > 0 (+inf allowed)");
+  if (int rc = check_sampling("bmpc_rollout_price", (int)price->S, w, 3, "w_fall, w_slip and w_unloaded", price->temperature); rc != BMPC_OK)
+    return rc;
   if (price->tilt_max != price->tilt_max || price->z_min != price->z_min)
     return fail(BMPC_ERR_INVALID, "bmpc_rollout_price: thresholds tilt_max and z_min must not be NaN");
   if (!(price->fz_floor >= 0.0)) return fail(BMPC_ERR_INVALID, "fz_floor must be >= 0 and not NaN");
@@ -1509,23 +1515,12 @@ static int rollout_check(bmpc_handle h, int B, const float* x_fb, const float* f
   return check_batch(h, B);
 }
 
-// The launches, on device-addressable arrays; d: the slots of bmpc_rollout_out in its order.  The reductions read scores and
-// weights on the device: where the caller wants neither array they live in the handle's `samples` scratch, as for
-// bmpc_evaluate_samples (a call that has to grow it is not asynchronous).
+// The launches, on device-addressable arrays; d: the slots of bmpc_rollout_out in its order.  (The roll-out kernel stores scores
+// only where it has an array for them: score scratch is needed only when reducing.)
 static int rollout_launch(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact, const float* x_cmd,
                           const float* x_ref, const float* push, const float* controls, const bmpc_plant& o,
                           const bmpc_plant_body* body, const bmpc_plant_ground* ground, const bmpc_rollout_price& price,
                           void* const* d, hipStream_t st) {
-  const size_t n = (size_t)B * (size_t)price.S;
-  bool reduce = false;
-  for (int i = RO_REDUCED; i < N_RO; ++i) reduce = reduce || d[i];
-  double *score = (double*)d[RO_SCORE], *weights = (double*)d[RO_WEIGHTS];
-  const size_t need = (reduce && !score ? n : 0) + (reduce && !weights ? n : 0);
-  if (need) {
-    HIP_TRY(h->samples.ensure(need));
-    if (!score) score = h->samples.p;
-    if (!weights) weights = h->samples.p + (need - n);
-  }
   const bmpc_params& p = h->params;
   bmpc::RolloutCost C;
   for (int i = 0; i < 12; ++i) { C.Q[i] = p.Q[i]; C.R[i] = p.R[i]; C.x_cmd[i] = p.x_cmd[i]; }
@@ -1534,19 +1529,14 @@ static int rollout_launch(bmpc_handle h, int B, const float* x_fb, const float* 
                               bd ? body->g : nullptr, ground ? ground->mu : nullptr, p.mu, ground ? 1 : 0, o.move_feet != 0 ? 1 : 0,
                               o.push_from, o.push_steps};
   const bmpc::RolloutPrice pr = {price.tilt_max, price.z_min, price.fz_floor, price.w_fall, price.w_slip, price.w_unloaded};
-  const bmpc::RolloutOut out = {(double*)d[0], score, (float*)d[2], (float*)d[3], (float*)d[4], (int32_t*)d[5], (float*)d[6],
-                                (float*)d[7], (int32_t*)d[8], (int32_t*)d[9], (int32_t*)d[10], (float*)d[11]};
-  const size_t blocks = (n + bmpc::ROLLOUT_NT - 1) / bmpc::ROLLOUT_NT;       // (at most 2^24: B, S <= 65536)
-  hipLaunchKernelGGL(bmpc::plant_rollout_samples_kernel, dim3((unsigned)blocks), dim3(bmpc::ROLLOUT_NT), 0, st, plant_params(h),
-                     bmpc::plant_scheme(p.dt, o.integrator, o.substeps), C, in, pr, out, B, (int)price.S);
-  HIP_TRY(hipGetLastError());
-  if (reduce) {
-    hipLaunchKernelGGL(bmpc::sample_reduce_kernel, dim3((unsigned)B), dim3(bmpc::REDUCE_NT), 0, st, (int)p.h, (int)price.S,
-                       price.temperature, (const double*)score, controls,
-                       bmpc::ReduceOut{(int32_t*)d[12], (int32_t*)d[13], weights, (double*)d[15], (double*)d[16]});
-    HIP_TRY(hipGetLastError());
-  }
-  return BMPC_OK;
+  const size_t blocks = ((size_t)B * (size_t)price.S + bmpc::ROLLOUT_NT - 1) / bmpc::ROLLOUT_NT;       // (at most 2^24: B, S <= 65536)
+  return launch_sampled(h, B, (int)price.S, price.temperature, false, (double*)d[RO_SCORE], controls, d + RO_REDUCED, st, [&](double* score) {
+    const bmpc::RolloutOut out = {(double*)d[0], score, (float*)d[2], (float*)d[3], (float*)d[4], (int32_t*)d[5], (float*)d[6],
+                                  (float*)d[7], (int32_t*)d[8], (int32_t*)d[9], (int32_t*)d[10], (float*)d[11]};
+    hipLaunchKernelGGL(bmpc::plant_rollout_samples_kernel, dim3((unsigned)blocks), dim3(bmpc::ROLLOUT_NT), 0, st, plant_params(h),
+                       bmpc::plant_scheme(p.dt, o.integrator, o.substeps), C, in, pr, out, B, (int)price.S);
+    return (int)BMPC_OK;
+  });
 }
 
 int bmpc_plant_rollout_samples_device(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
@@ -1562,7 +1552,6 @@ int bmpc_plant_rollout_samples_device(bmpc_handle h, int B, const float* x_fb, c
   return rollout_launch(h, B, x_fb, foot, contact, x_cmd, x_ref, push, controls, o, body, ground, *price, d, pick_stream(h, stream));
 }
 
-// (staging: one block of the handle for the inputs and one for the wanted outputs, every array on an 8-byte boundary)
 int bmpc_plant_rollout_samples(bmpc_handle h, int B, const float* x_fb, const float* foot, const uint8_t* contact,
                                const float* x_cmd, const float* x_ref, const float* push, const float* controls,
                                const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
@@ -1571,40 +1560,17 @@ int bmpc_plant_rollout_samples(bmpc_handle h, int B, const float* x_fb, const fl
   bmpc_plant o;
   if (int rc = rollout_check(h, B, x_fb, foot, contact, controls, plant, ground, price, out, slots, &o); rc <= 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t n = (size_t)B, H = (size_t)h->dev.h, S = (size_t)price->S;
-  constexpr int N_RI = 11;
-  const void* src[N_RI] = {x_fb, foot, contact, x_cmd, x_ref, push, controls, body ? body->m : nullptr, body ? body->I : nullptr,
-                           body ? body->g : nullptr, ground ? ground->mu : nullptr};
-  const size_t in_bytes[N_RI] = {n * 48, n * 24, n * H * 2, n * 48, n * H * 48, n * 24, n * S * H * 48, n * 8, n * 72, n * 8, n * 16};
-  size_t in_off[N_RI], out_off[N_RO], out_bytes[N_RO], tot = 0;              // offsets and totals in doubles
-  for (int i = 0; i < N_RI; ++i) { in_off[i] = tot; tot += src[i] ? (in_bytes[i] + 7) / 8 : 0; }
-  HIP_TRY(h->rollout_in.ensure(tot));
-  hipStream_t st = h->stream;
-  const void* din[N_RI];
-  for (int i = 0; i < N_RI; ++i) {
-    din[i] = src[i] ? h->rollout_in.p + in_off[i] : nullptr;
-    if (src[i]) HIP_TRY(hipMemcpyAsync(h->rollout_in.p + in_off[i], src[i], in_bytes[i], hipMemcpyHostToDevice, st));
-  }
-  tot = 0;
-  for (int i = 0; i < N_RO; ++i) {
-    out_bytes[i] = slots.s[i].p ? n * slots.s[i].w.bytes(H) : 0;
-    out_off[i] = tot;
-    tot += (out_bytes[i] + 7) / 8;
-  }
-  HIP_TRY(h->rollout_out.ensure(tot));
-  void* d[N_RO];
-  for (int i = 0; i < N_RO; ++i) d[i] = slots.s[i].p ? h->rollout_out.p + out_off[i] : nullptr;
-  const bmpc_plant_body d_body = {(const double*)din[7], (const double*)din[8], (const double*)din[9]};
-  const bmpc_plant_ground d_ground = {(const double*)din[10]};
-  if (int rc = rollout_launch(h, B, (const float*)din[0], (const float*)din[1], (const uint8_t*)din[2], (const float*)din[3],
-                              (const float*)din[4], (const float*)din[5], (const float*)din[6], o, body ? &d_body : nullptr,
-                              ground ? &d_ground : nullptr, *price, d, st);
-      rc != BMPC_OK)
-    return rc;
-  for (int i = 0; i < N_RO; ++i)
-    if (slots.s[i].p) HIP_TRY(hipMemcpyAsync(slots.s[i].p, d[i], out_bytes[i], hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return BMPC_OK;
+  const InSlot in[11] = {{x_fb, IN[I_XFB].w}, {foot, IN[I_FOOT].w}, {contact, IN[I_CON].w}, {x_cmd, IN[I_XCMD].w}, {x_ref, IN[I_XREF].w},
+                         {push, W_WRENCH}, {controls, controls_width((size_t)price->S)}, {body ? body->m : nullptr, W_MASS},
+                         {body ? body->I : nullptr, W_INERTIA}, {body ? body->g : nullptr, W_GRAVITY},
+                         {ground ? ground->mu : nullptr, W_GROUND_MU}};
+  Slices<11> d; Slices<N_RO> r;
+  if (int rc = stage(h, B, in, &d, slots.s, &r); rc != BMPC_OK) return rc;
+  const bmpc_plant_body d_body = {d.at<double>(7), d.at<double>(8), d.at<double>(9)};
+  const bmpc_plant_ground d_ground = {d.at<double>(10)};
+  const int rc = rollout_launch(h, B, d.at<float>(0), d.at<float>(1), d.at<uint8_t>(2), d.at<float>(3), d.at<float>(4), d.at<float>(5),
+                              d.at<float>(6), o, body ? &d_body : nullptr, ground ? &d_ground : nullptr, *price, r.d, h->stream);
+  return rc != BMPC_OK ? rc : fetch(h, slots.s, r);
 }
 
 int bmpc_set_dispatch_order(bmpc_handle h, const int32_t* order_dev, int longest_first_rollouts) {

@@ -71,7 +71,7 @@ CONFIGS = {
 # rebuilds all of them.  bmpc_capi.hip, the first, is the translation unit that includes the others.
 KERNEL_SOURCES = ("bmpc_capi.hip", "bmpc_kernels.hip", "bmpc_stage.hip", "bmpc_lowlevel.hip", "bmpc_evaluate.hip", "bmpc_evaluate_grad.hip",
                   "bmpc_certify.hip", "bmpc_evaluate_samples.hip", "bmpc_plant.hip", "bmpc_plant_rollout.hip", "bmpc_model.hip",
-                  "bmpc_host_params.hpp")
+                  "bmpc_host_params.hpp", "bmpc_host_staging.hpp")
 
 
 def kernel_source_paths():
