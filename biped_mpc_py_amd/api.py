@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .params import pack_params, params_key
+from .params import MPC, pack_params, params_key
 
 
 def phase_index(t, mpc_or_dt, h=None):
@@ -137,30 +137,62 @@ def duals_to_reference_order(lam):
                            lam[..., 32:36].reshape(lead + (4 * h,))], -1)
 
 
-# The evaluation family (`bmpc_evaluate`, `bmpc_evaluate_grad`, `bmpc_certify` and their _device twins): per operation the ctypes
-# output descriptor, the host and the device entry, whether the entries take `act_tol`, and the outputs in the order of the result
-# dict: (name, dtype, shape in terms of "B", "h" and -- evaluate_samples -- "S").  `BatchSolver._eval_host` / `_eval_device` do the
-# work for the rows with one plan per instance, `_samples_host` / `evaluate_samples_device` for the row with S of them.
+# The evaluation family (`bmpc_evaluate`, `bmpc_evaluate_grad`, `bmpc_certify`, `bmpc_evaluate_samples` and their _device twins):
+# per operation the ctypes output descriptor, the host entry (the device entry is the same name + "_device"), the shape of
+# `controls` -- with an "S" in it the entries take a `bmpc_samples` descriptor --, whether the entries take `act_tol`, and the
+# outputs in the order of the result dict: (name, dtype, shape).  Shapes are in terms of "B", "h" and "S".  `BatchSolver._eval` is
+# the one body of all four rows, for host arrays and device tensors alike (`_Host` / `_Device`); `_eval_host` does a host call's
+# lenient conversions before it.
 _EVAL_OPS = {
-    "evaluate": (_lib.CEvalOut, "bmpc_evaluate", "bmpc_evaluate_device", False,
+    "evaluate": (_lib.CEvalOut, "bmpc_evaluate", ("B", "h", 12), False,
                  (("cost", "float64", ("B",)), ("objective", "float64", ("B",)), ("violation", "float64", ("B", 4)),
                   ("states", "float64", ("B", "h", 13)))),
-    "evaluate_grad": (_lib.CGradOut, "bmpc_evaluate_grad", "bmpc_evaluate_grad_device", False,
+    "evaluate_grad": (_lib.CGradOut, "bmpc_evaluate_grad", ("B", "h", 12), False,
                       (("cost", "float64", ("B",)), ("grad_u", "float64", ("B", "h", 12)), ("grad_x0", "float64", ("B", 12)))),
-    "certify": (_lib.CCertOut, "bmpc_certify", "bmpc_certify_device", True,
+    "certify": (_lib.CCertOut, "bmpc_certify", ("B", "h", 12), True,
                 (("lam", "float64", ("B", "h", 36)), ("resid", "float64", ("B", "h", 12)), ("summary", "float64", ("B", 4)),
                  ("n_active", "int32", ("B",)), ("status", "int32", ("B",)))),
-    "evaluate_samples": (_lib.CSamplesOut, "bmpc_evaluate_samples", "bmpc_evaluate_samples_device", False,
+    "evaluate_samples": (_lib.CSamplesOut, "bmpc_evaluate_samples", ("B", "S", "h", 12), False,
                          (("cost", "float64", ("B", "S")), ("violation", "float64", ("B", "S", 4)), ("score", "float64", ("B", "S")),
                           ("best", "int32", ("B",)), ("n_valid", "int32", ("B",)), ("weights", "float64", ("B", "S")),
                           ("u_mean", "float64", ("B", "h", 12)), ("ess", "float64", ("B",)))),
 }
 
+# The arguments of the entry families as rows (name, dtype, shape), in the order of the entries' argument lists, each table a
+# function of the call's dimensions (a device call forms the rows once; a host call, whose arrays are exact already, never does).
+def _input_rows(B, h, S=None):
+    """The members of `bmpc_inputs` in its order, then the `controls` of the evaluation family ((B,S,h,12) with S plans each)."""
+    return (("x_fb", "float32", (B, 12)), ("foot", "float32", (B, 6)), ("contact", "uint8", (B, h, 2)), ("phase", "int32", (B,)),
+            ("x_cmd", "float32", (B, 12)), ("mu", "float32", (B, h, 2)), ("x_ref", "float32", (B, h, 12)),
+            ("foot_ref", "float32", (B, h, 6)), ("controls", "float32", (B, h, 12) if S is None else (B, S, h, 12)))
+
+
+def _solve_output_rows(B, h, S=None):
+    return (("controls", "float32", (B, h, 12)), ("states", "float32", (B, h, 13)), ("iters", "int32", (B,)),
+            ("residuals", "float32", (B, 2)), ("status", "int32", (B,)), ("nfactor", "int32", (B,)))
+
+
+def _loop_rows(B, h, S=None):
+    """What the closed loops (`rollout_device`, `simulate_device`) advance in place, then their optional inputs."""
+    return (("x_fb", "float32", (B, 12)), ("foot", "float32", (B, 6)), ("t", "float64", (B,)),
+            ("x_cmd", "float32", (B, 12)), ("mu", "float32", (B, h, 2)), ("push", "float32", (B, 6)))
+
+
+def _step_rows(B, h=None, S=None):
+    return (("x_fb", "float32", (B, 12)), ("u0", "float32", (B, 12)), ("foot", "float32", (B, 6)), ("contact0", "uint8", (B, 2)),
+            ("wrench", "float32", (B, 6)), ("x_next", "float32", (B, 12)))
+
+
+def _rollout_input_rows(B, h, S):
+    return (("x_fb", "float32", (B, 12)), ("foot", "float32", (B, 6)), ("contact", "uint8", (B, h, 2)), ("x_cmd", "float32", (B, 12)),
+            ("x_ref", "float32", (B, h, 12)), ("push", "float32", (B, 6)), ("controls", "float32", (B, S, h, 12)))
+
+
 SAMPLES_MAX = 65536     # samples per instance `evaluate_samples` takes (include/bmpc.h)
 
 
 def _shape(spec, B, h, S=None):
-    return tuple({"B": B, "h": h, "S": S}.get(d, d) for d in spec)
+    return tuple(B if d == "B" else h if d == "h" else S if d == "S" else d for d in spec)
 
 
 def _samples_f32(controls, h, B=None):
@@ -179,10 +211,39 @@ def _samples_desc(S, w_viol, temperature):
     w = np.asarray(w_viol, np.float64).reshape(-1)
     if w.shape != (4,) or not (np.isfinite(w).all() and (w >= 0).all()):
         raise ValueError("w_viol must be four finite prices >= 0 (friction, force box, moment box, line foot)")
+    return _lib.CSamples(int(S), 0, (C.c_double * 4)(*w), _temperature(temperature))
+
+
+# The scalar options more than one entry family takes, each checked as the library checks it (ValueError) and returned as a float.
+def _temperature(temperature):
     T = float(temperature)
     if not T > 0.0:
         raise ValueError("temperature must be > 0 (inf: uniform weights)")
-    return _lib.CSamples(int(S), 0, (C.c_double * 4)(*w), T)
+    return T
+
+
+def _fall(fall):
+    try:
+        tilt_max, z_min = (float(v) for v in fall)
+    except (TypeError, ValueError):
+        raise ValueError("fall must be a (tilt_max, z_min) pair") from None
+    if tilt_max != tilt_max or z_min != z_min:
+        raise ValueError("fall thresholds must not be NaN")
+    return tilt_max, z_min
+
+
+def _fz_floor(fz_floor):
+    floor = float(fz_floor)
+    if not floor >= 0.0:
+        raise ValueError("fz_floor must be >= 0 and not NaN")
+    return floor
+
+
+def _act_tol(act_tol):
+    tol = float(act_tol)
+    if tol != tol:
+        raise ValueError("act_tol must not be NaN")
+    return tol
 
 
 def _ptr(a):
@@ -191,14 +252,84 @@ def _ptr(a):
     return None if a is None else a.__array_interface__["data"][0]
 
 
-def _tensor_ptr(t, dtype, shape, dev):
-    """Device address of a tensor argument of the device-resident methods (None for None): it must be a contiguous `dtype` tensor
-    of `shape` on `dev` (ValueError)."""
-    if t is None:
+# Where the arrays of a call live.  Past a host method's conversions a host call and a device call are the same thing -- exactly-typed
+# arrays in a space -- and the body of an entry family is written once over these operations:
+#   ptrs(rows, values, B, h, S)        the addresses of a method's arguments, one per row of the table `rows(B, h, S)`.  On the
+#                                      device each tensor is held to its row (`ptr`); on the host the method's own conversions have
+#                                      just made every array exact, and the addresses are taken as they are;
+#   ptr(name, value, dtype, *shapes)   the address of an array the CALLER supplies as it is: exactly of `dtype` (a name: "float32")
+#                                      and of one of `shapes` (None for None), or ValueError naming the argument;
+#   empty(dtype, shape), address(a)    an uninitialised output, and the address of an array the binding made itself;
+#   suffix, tail, empty_is_null        what the entry's name and its argument list end in, and whether an array without elements
+#                                      has no address to hand over.
+class _Host:
+    """NumPy arrays.  A copy that `ptr` had to make (a list, a non-contiguous array) is kept until the space goes, past the call."""
+    suffix, tail, empty_is_null, keep = "", (), False, ()
+    address = staticmethod(_ptr)
+
+    @staticmethod
+    def ptrs(rows, values, B, h=None, S=None):
+        return [None if a is None else a.__array_interface__["data"][0] for a in values]
+
+    def ptr(self, name, value, dtype, *shapes):
+        if value is None:
+            return None
+        a = np.asarray(value)
+        if a.dtype != dtype or a.shape not in shapes:
+            raise ValueError(f"{name} must be {dtype} of shape {' or '.join(map(str, shapes))}, not {a.dtype} {a.shape}")
+        a = np.ascontiguousarray(a)
+        if a is not value:
+            self.keep += (a,)
+        return a.__array_interface__["data"][0]
+
+    @staticmethod
+    def empty(dtype, shape):
+        return np.empty(shape, dtype)
+
+
+class _Device:
+    """Contiguous torch tensors on the solver's device `index`, which `dev` (the device of the call's first tensor) must be; the
+    call is asynchronous on `stream`, a raw hipStream_t value (None: torch's current stream)."""
+    suffix, empty_is_null = "_device", True
+
+    def __init__(self, index, dev, stream):
+        import torch
+        if dev.type != "cuda" or dev.index != index:
+            raise ValueError(f"tensors must live on cuda:{index}")
+        self.torch, self.dev = torch, dev
+        self.tail = (torch.cuda.current_stream(dev).cuda_stream if stream is None else stream,)
+
+    def ptrs(self, rows, values, B, h=None, S=None):
+        return [None if t is None else self.ptr(name, t, dtype, shape) for (name, dtype, shape), t in zip(rows(B, h, S), values)]
+
+    def ptr(self, name, value, dtype, *shapes):
+        if value is None:
+            return None
+        t = value
+        if not isinstance(t, self.torch.Tensor) or t.device != self.dev or t.dtype != getattr(self.torch, dtype) \
+                or not t.is_contiguous() or tuple(t.shape) not in shapes:
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {' or '.join(map(str, shapes))} on {self.dev}")
+        return t.data_ptr()
+
+    def empty(self, dtype, shape):
+        return self.torch.empty(shape, dtype=getattr(self.torch, dtype), device=self.dev)
+
+    @staticmethod
+    def address(t):
+        return t.data_ptr()
+
+
+def _host_array(name, value, shape, dtype=np.float32, required=True):
+    """An argument of the strict host methods: any array of exactly `shape` (ValueError naming the argument), converted to
+    C-contiguous `dtype`; None stays None unless `required`."""
+    if value is None:
+        if required:
+            raise ValueError(f"{name} is required")
         return None
-    if t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
-        raise ValueError(f"expected contiguous {dtype} tensor of shape {shape} on {dev}")
-    return t.data_ptr()
+    a = np.asarray(value)
+    if a.shape != shape:
+        raise ValueError(f"{name} must have shape {shape}, not {a.shape}")
+    return np.ascontiguousarray(a, dtype)
 
 
 class _HandleOwner:
@@ -397,43 +528,47 @@ class BatchSolver:
         return self._samples_host(x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, w_viol, temperature)
 
     def _samples_host(self, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, w_viol, temperature, skip=()):
-        """The host entry of row "evaluate_samples" of `_EVAL_OPS`: as `_eval_host`, with S plans per instance."""
-        struct, entry, _, _, outputs = _EVAL_OPS["evaluate_samples"]
-        c32 = _samples_f32(controls, self.h)
-        B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
-        if c32.shape[0] != B:
-            raise ValueError(f"controls must have shape ({B}, S, {self.h}, 12), got {c32.shape}")
-        S = c32.shape[1]
-        smp = _samples_desc(S, w_viol, temperature)
-        x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h, finite=False)
-        if foot is None and foot_ref is None:
-            raise ValueError("foot is required unless foot_ref is given")
-        res = {k: None if k in skip else np.empty(_shape(shp, B, self.h, S), dt) for k, dt, shp in outputs}
-        inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
-        out = struct(**{k: _ptr(v) for k, v in res.items()})
-        _lib.check(getattr(self._lib, entry)(self._h, B, C.byref(inp), _ptr(c32), C.byref(smp), C.byref(out)))
-        return res
+        """The host entry of row "evaluate_samples" of `_EVAL_OPS`: `_eval_host` with S plans per instance."""
+        return self._eval_host("evaluate_samples", x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref,
+                               samples=(w_viol, temperature), skip=skip)
 
-    def _eval_host(self, kind, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, act_tol=None, skip=()):
-        """The host entry of row `kind` of `_EVAL_OPS`: host arrays marshalled as `solve` does, outputs allocated (None for those
-        named in `skip`), one call.  Returns the dict of outputs."""
-        struct, entry, _, takes_tol, outputs = _EVAL_OPS[kind]
-        c32 = _controls_f32(controls, self.h)
+    def _eval_host(self, kind, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, act_tol=None, samples=None, skip=()):
+        """The host entry of row `kind` of `_EVAL_OPS`: host arrays marshalled as `solve` does, then `_eval`."""
+        per_sample = "S" in _EVAL_OPS[kind][2]
+        c32 = (_samples_f32 if per_sample else _controls_f32)(controls, self.h)
         B, x_fb, foot, contact, phase, x_cmd, mu = self._marshal(x_fb, foot, contact, phase, x_cmd, mu)
         if c32.shape[0] != B:
-            raise ValueError(f"controls must have shape ({B}, {self.h}, 12), got {c32.shape}")
+            raise ValueError(f"controls must have shape ({B}, {'S, ' if per_sample else ''}{self.h}, 12), got {c32.shape}")
         x_ref, foot_ref = _kernel_refs(x_ref, foot_ref, B, self.h, finite=False)
         if foot is None and foot_ref is None:
             raise ValueError("foot is required unless foot_ref is given")
-        tol = ()
+        return self._eval(_Host(), kind, B, (x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref, c32), {}, act_tol, samples, skip)
+
+    def _eval(self, space, kind, B, inputs, given, act_tol=None, samples=None, skip=()):
+        """Row `kind` of `_EVAL_OPS` on exactly-typed arrays in `space`: `inputs` are the members of `bmpc_inputs` in its order and
+        `controls`, `given` maps outputs to the caller's arrays (the others are allocated here, unless named in `skip`: those stay
+        None and are not computed), `samples` is (w_viol, temperature) for the row with S plans per instance.  One call; returns
+        the dict of outputs."""
+        struct, entry, u_shape, takes_tol, outputs = _EVAL_OPS[kind]
+        h, S, mid = self.h, None, ()
         if takes_tol:
-            tol = (float(act_tol),)
-            if tol[0] != tol[0]:
-                raise ValueError("act_tol must not be NaN")
-        res = {k: None if k in skip else np.empty(_shape(shp, B, self.h), dt) for k, dt, shp in outputs}
-        inp = _lib.CInputs(_ptr(x_fb), _ptr(foot), _ptr(contact), _ptr(phase), _ptr(x_cmd), _ptr(mu), _ptr(x_ref), _ptr(foot_ref))
-        out = struct(**{k: _ptr(v) for k, v in res.items()})
-        _lib.check(getattr(self._lib, entry)(self._h, B, C.byref(inp), _ptr(c32), *tol, C.byref(out)))
+            mid += (_act_tol(act_tol),)
+        if "S" in u_shape:
+            controls = inputs[-1]
+            if len(controls.shape) != 4 or not 1 <= controls.shape[1] <= SAMPLES_MAX:
+                raise ValueError(f"controls must have shape ({B}, S, {h}, 12) with 1 <= S <= {SAMPLES_MAX}, got {tuple(controls.shape)}")
+            S = int(controls.shape[1])
+            mid += (C.byref(_samples_desc(S, *samples)),)
+        res, out = {}, struct()
+        for k, dtype, shape in outputs:
+            a = res[k] = given.get(k)
+            if a is not None:
+                setattr(out, k, space.ptr(k, a, dtype, _shape(shape, B, h, S)))
+            elif k not in skip:
+                a = res[k] = space.empty(dtype, _shape(shape, B, h, S))
+                setattr(out, k, space.address(a))
+        *inp, u = space.ptrs(_input_rows, inputs, B, h, S)
+        _lib.check(getattr(self._lib, entry + space.suffix)(self._h, B, C.byref(_lib.CInputs(*inp)), u, *mid, C.byref(out), *space.tail))
         return res
 
     def _io_views(self, B, with_x_cmd, with_mu, with_states):
@@ -534,33 +669,18 @@ class BatchSolver:
         surrounding torch work like any torch kernel.  `x_ref` (B,h,12) / `foot_ref` (B,h,6) float32 tensors: references to track
         (`bmpc_solve_inputs_device`); `foot` may then be None if `foot_ref` is given.  Their values are not checked here (that
         would synchronise): a non-finite one shows as status 2 of its instance."""
-        import torch
+        space = _Device(self.device, x_fb.device, stream)
         B = x_fb.shape[0]
         h = self.h
-        dev = x_fb.device
-        if dev.type != "cuda" or dev.index != self.device:
-            raise ValueError(f"tensors must live on cuda:{self.device}")
         if controls is None:
-            controls = torch.empty((B, h, 12), dtype=torch.float32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        inp = self._device_inputs(dev, B, x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref)
-        out = [_tensor_ptr(t, dtype, shape, dev) for t, dtype, shape in (
-            (controls, torch.float32, (B, h, 12)), (states, torch.float32, (B, h, 13)), (iters, torch.int32, (B,)),
-            (residuals, torch.float32, (B, 2)), (status, torch.int32, (B,)), (nfactor, torch.int32, (B,)))]
+            controls = space.empty("float32", (B, h, 12))
+        inp = space.ptrs(_input_rows, (x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref), B, h)
+        out = space.ptrs(_solve_output_rows, (controls, states, iters, residuals, status, nfactor), B, h)
         if x_ref is not None or foot_ref is not None:
-            _lib.check(self._lib.bmpc_solve_inputs_device(self._h, B, C.byref(_lib.CInputs(*inp)), *out, st))
+            _lib.check(self._lib.bmpc_solve_inputs_device(self._h, B, C.byref(_lib.CInputs(*inp)), *out, *space.tail))
         else:
-            _lib.check(self._lib.bmpc_solve_batch_device(self._h, B, *inp[:6], *out, st))
+            _lib.check(self._lib.bmpc_solve_batch_device(self._h, B, *inp[:6], *out, *space.tail))
         return controls, states
-
-    def _device_inputs(self, dev, B, x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref):
-        """The members of `bmpc_inputs` as device addresses, in its order (None: NULL), every tensor checked (`_tensor_ptr`)."""
-        import torch
-        h = self.h
-        return [_tensor_ptr(t, dtype, shape, dev) for t, dtype, shape in (
-            (x_fb, torch.float32, (B, 12)), (foot, torch.float32, (B, 6)), (contact, torch.uint8, (B, h, 2)), (phase, torch.int32, (B,)),
-            (x_cmd, torch.float32, (B, 12)), (mu, torch.float32, (B, h, 2)), (x_ref, torch.float32, (B, h, 12)),
-            (foot_ref, torch.float32, (B, h, 6)))]
 
     def evaluate_device(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None,
                         cost=None, objective=None, violation=None, states=None, want_states=False, stream=None):
@@ -602,61 +722,17 @@ class BatchSolver:
         -- all of them, or with `want` (names) only those named or passed; the others stay None and are not computed (a call that
         wants no reduced output is one launch, else two).  Asynchronous on `stream` (default: torch's current stream) unless the
         handle's scratch has to grow (include/bmpc.h); nothing crosses PCIe.  Returns the dict of outputs."""
-        import torch
-        struct, _, entry, _, outputs = _EVAL_OPS["evaluate_samples"]
-        h = self.h
-        dev = x_fb.device
-        if dev.type != "cuda" or dev.index != self.device:
-            raise ValueError(f"tensors must live on cuda:{self.device}")
-        B = x_fb.shape[0]
-        if controls.dim() != 4 or not 1 <= controls.shape[1] <= SAMPLES_MAX:
-            raise ValueError(f"controls must have shape ({B}, S, {h}, 12) with 1 <= S <= {SAMPLES_MAX}, got {tuple(controls.shape)}")
-        S = int(controls.shape[1])
-        smp = _samples_desc(S, w_viol, temperature)
         given = dict(cost=cost, violation=violation, score=score, best=best, n_valid=n_valid, weights=weights, u_mean=u_mean, ess=ess)
         if want is not None and not set(want) <= set(given):
             raise ValueError(f"want names outputs among {sorted(given)}")
-        res = {}
-        for k, dt, shp in outputs:
-            t = given[k]
-            if t is None and (want is None or k in want):
-                t = torch.empty(_shape(shp, B, h, S), dtype=getattr(torch, dt), device=dev)
-            res[k] = t
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        inp = _lib.CInputs(*self._device_inputs(dev, B, x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref))
-        out = struct(**{k: _tensor_ptr(res[k], getattr(torch, dt), _shape(shp, B, h, S), dev) for k, dt, shp in outputs})
-        u = _tensor_ptr(controls, torch.float32, (B, S, h, 12), dev)
-        _lib.check(getattr(self._lib, entry)(self._h, B, C.byref(inp), u, C.byref(smp), C.byref(out), st))
-        return res
+        return self._eval_device("evaluate_samples", x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, given,
+                                 samples=(w_viol, temperature), skip=() if want is None else set(given) - set(want), stream=stream)
 
-    def _eval_device(self, kind, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, given, act_tol=None, skip=(),
-                     stream=None):
-        """The device entry of row `kind` of `_EVAL_OPS` on CUDA(HIP) torch tensors: `given` maps every output to the caller's
-        tensor or None (allocated here, unless named in `skip`: then it stays None).  Returns the dict of output tensors."""
-        import torch
-        struct, _, entry, takes_tol, outputs = _EVAL_OPS[kind]
-        B = x_fb.shape[0]
-        h = self.h
-        dev = x_fb.device
-        if dev.type != "cuda" or dev.index != self.device:
-            raise ValueError(f"tensors must live on cuda:{self.device}")
-        tol = ()
-        if takes_tol:
-            tol = (float(act_tol),)
-            if tol[0] != tol[0]:
-                raise ValueError("act_tol must not be NaN")
-        res = {}
-        for k, dt, shp in outputs:
-            t = given[k]
-            if t is None and k not in skip:
-                t = torch.empty(_shape(shp, B, h), dtype=getattr(torch, dt), device=dev)
-            res[k] = t
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        inp = _lib.CInputs(*self._device_inputs(dev, B, x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref))
-        out = struct(**{k: _tensor_ptr(res[k], getattr(torch, dt), _shape(shp, B, h), dev) for k, dt, shp in outputs})
-        u = _tensor_ptr(controls, torch.float32, (B, h, 12), dev)
-        _lib.check(getattr(self._lib, entry)(self._h, B, C.byref(inp), u, *tol, C.byref(out), st))
-        return res
+    def _eval_device(self, kind, x_fb, foot, contact, phase, controls, x_cmd, mu, x_ref, foot_ref, given, act_tol=None, samples=None,
+                     skip=(), stream=None):
+        """The device entry of row `kind` of `_EVAL_OPS` on CUDA(HIP) torch tensors: `_eval` on this solver's device and `stream`."""
+        return self._eval(_Device(self.device, x_fb.device, stream), kind, x_fb.shape[0],
+                          (x_fb, foot, contact, phase, x_cmd, mu, x_ref, foot_ref, controls), given, act_tol, samples, skip)
 
     def cost_torch(self, x_fb, foot, contact, phase, controls, x_cmd=None, mu=None, x_ref=None, foot_ref=None):
         """`evaluate`'s cost as a differentiable torch value: float64 tensor (B,) on the device, with gradients to `controls` (B,h,12)
@@ -725,19 +801,16 @@ class BatchSolver:
     def contact_sequence_device(self, t, phase=None, contact=None, period=None, offset=None, duty=None, stream=None):
         """`contact_sequence` on device tensors: t (B,) float64 CUDA tensor -> (phase int32 (B,), contact uint8
         (B,h,2)), asynchronous on `stream` (default: torch's current stream); nothing crosses PCIe."""
-        import torch
-        dev = t.device
-        if dev.type != "cuda" or dev.index != self.device or t.dtype != torch.float64 or not t.is_contiguous():
-            raise ValueError(f"t must be a contiguous float64 tensor on cuda:{self.device}")
+        space = _Device(self.device, t.device, stream)
         B = t.shape[0]
+        tp = space.ptr("t", t, "float64", tuple(t.shape))
         if phase is None:
-            phase = torch.empty(B, dtype=torch.int32, device=dev)
+            phase = space.empty("int32", (B,))
         if contact is None:
-            contact = torch.empty((B, self.h, 2), dtype=torch.uint8, device=dev)
+            contact = space.empty("uint8", (B, self.h, 2))
         gait = self._gait(period, offset, duty)
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        _lib.check(self._lib.bmpc_contact_sequence_device(self._h, B, t.data_ptr(), None if gait is None else C.byref(gait),
-                                                          phase.data_ptr(), contact.data_ptr(), st))
+        _lib.check(self._lib.bmpc_contact_sequence_device(self._h, B, tp, None if gait is None else C.byref(gait),
+                                                          phase.data_ptr(), contact.data_ptr(), *space.tail))
         return phase, contact
 
     # ---- receding-horizon use (SURVEY 8(f) row 3) --------------------------------------------------
@@ -768,22 +841,17 @@ class BatchSolver:
         """`steps` closed-loop control periods on device tensors (`bmpc_rollout_device`): x_fb (B,12) float32 and
         t (B,) float64 are advanced IN PLACE; returns dict(u0 (steps,B,12), x (steps,B,12), iters (steps,B) | None,
         status_any (B,)).  Asynchronous on `stream` (default: torch's current stream)."""
-        import torch
-        dev = x_fb.device
+        space = _Device(self.device, x_fb.device, stream)
         B = x_fb.shape[0]
-        if dev.type != "cuda" or dev.index != self.device:
-            raise ValueError(f"tensors must live on cuda:{self.device}")
         gait = self._gait(period, offset, duty)
-        u0 = torch.empty((steps, B, 12), dtype=torch.float32, device=dev)
-        xt = torch.empty((steps, B, 12), dtype=torch.float32, device=dev)
-        its = torch.empty((steps, B), dtype=torch.int32, device=dev) if want_iters else None
-        st_any = torch.empty(B, dtype=torch.int32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        u0 = space.empty("float32", (steps, B, 12))
+        xt = space.empty("float32", (steps, B, 12))
+        its = space.empty("int32", (steps, B)) if want_iters else None
+        st_any = space.empty("int32", (B,))
+        a = space.ptrs(_loop_rows, (x_fb, foot, t, x_cmd, mu), B, self.h)
         _lib.check(self._lib.bmpc_rollout_device(
-            self._h, B, int(steps), _tensor_ptr(x_fb, torch.float32, (B, 12), dev), _tensor_ptr(foot, torch.float32, (B, 6), dev),
-            _tensor_ptr(t, torch.float64, (B,), dev), None if gait is None else C.byref(gait),
-            _tensor_ptr(x_cmd, torch.float32, (B, 12), dev), _tensor_ptr(mu, torch.float32, (B, self.h, 2), dev),
-            u0.data_ptr(), xt.data_ptr(), None if its is None else its.data_ptr(), st_any.data_ptr(), st))
+            self._h, B, int(steps), *a[:3], None if gait is None else C.byref(gait), *a[3:],
+            u0.data_ptr(), xt.data_ptr(), None if its is None else its.data_ptr(), st_any.data_ptr(), *space.tail))
         return dict(u0=u0, x=xt, iters=its, status_any=st_any)
 
     # ---- the plant and the closed loop on it (bmpc_plant_step*, bmpc_simulate_device) ---------------
@@ -799,36 +867,17 @@ class BatchSolver:
         return _lib.CPlant(_lib.PLANT_INTEGRATORS[integrator], int(substeps), 1 if move_feet else 0, int(push_from), int(push_steps))
 
     @staticmethod
-    def _body_items(body):
-        """The members of a `body` mapping as (name, value, accepted shapes per B); an unknown key is a ValueError."""
+    def _body(space, body, B):
+        """A `body` mapping of float64 arrays in `space` -- any of m (B,), I (B,3,3) or (B,9), g (B,) -- as the `bmpc_plant_body`
+        argument of an entry (None for None); anything but a mapping with those keys is a ValueError."""
+        if body is None:
+            return None
         if not hasattr(body, "keys") or set(body.keys()) - {"m", "I", "g"}:
             raise ValueError("body must be a mapping with any of the keys 'm', 'I', 'g'")
-        return [(k, body.get(k), ((3, 3), (9,)) if k == "I" else ((),)) for k in ("m", "I", "g") if body.get(k) is not None]
-
-    @classmethod
-    def _body_host(cls, body, B):
-        """(`bmpc_plant_body` of host arrays, the arrays it points into) from a `body` mapping of float64 arrays."""
-        cb, keep = _lib.CPlantBody(), []
-        for k, v, shapes in cls._body_items(body):
-            v = np.asarray(v)
-            if v.dtype != np.float64 or v.shape[1:] not in shapes or v.shape[:1] != (B,):
-                raise ValueError(f"body[{k!r}] must be float64 of shape {' or '.join(str((B,) + s) for s in shapes)}, not {v.dtype} {v.shape}")
-            keep.append(np.ascontiguousarray(v))
-            setattr(cb, k, keep[-1].ctypes.data)
-        return cb, keep
-
-    @classmethod
-    def _body_device(cls, body, B, dev):
-        """`bmpc_plant_body` of device pointers from a `body` mapping of contiguous float64 tensors on `dev`."""
-        import torch
         cb = _lib.CPlantBody()
-        for k, v, shapes in cls._body_items(body):
-            if not isinstance(v, torch.Tensor) or v.dtype != torch.float64 or v.device != dev or not v.is_contiguous() \
-                    or tuple(v.shape[1:]) not in shapes or tuple(v.shape[:1]) != (B,):
-                raise ValueError(f"body[{k!r}] must be a contiguous float64 tensor on {dev} of shape "
-                                 f"{' or '.join(str((B,) + s) for s in shapes)}")
-            setattr(cb, k, v.data_ptr())
-        return cb
+        for k, shapes in (("m", ((B,),)), ("I", ((B, 3, 3), (B, 9))), ("g", ((B,),))):
+            setattr(cb, k, space.ptr(f"body[{k!r}]", body.get(k), "float64", *shapes))
+        return C.byref(cb)
 
     @staticmethod
     def _ground_mu(ground, want_applied=False):
@@ -843,28 +892,30 @@ class BatchSolver:
         return ground.get("mu")
 
     @classmethod
-    def _ground_host(cls, ground, B):
-        """(`bmpc_plant_ground` of a host array, the array it points into) from a `ground` mapping: mu float64 (B, 2) or absent."""
-        cg, mu = _lib.CPlantGround(), cls._ground_mu(ground)
-        if mu is not None:
-            mu = np.asarray(mu)
-            if mu.dtype != np.float64 or mu.shape != (B, 2):
-                raise ValueError(f"ground['mu'] must be float64 of shape {(B, 2)}, not {mu.dtype} {mu.shape}")
-            mu = np.ascontiguousarray(mu)
-            cg.mu = mu.ctypes.data
-        return cg, mu
+    def _ground(cls, space, ground, B):
+        """A `ground` mapping -- mu, a float64 array (B,2) in `space`, or absent -- as the `bmpc_plant_ground` argument of an entry
+        (None for None)."""
+        if ground is None:
+            return None
+        return C.byref(_lib.CPlantGround(space.ptr("ground['mu']", cls._ground_mu(ground), "float64", (B, 2))))
 
-    @classmethod
-    def _ground_device(cls, ground, B, dev):
-        """`bmpc_plant_ground` of a device pointer from a `ground` mapping: mu a contiguous float64 tensor (B, 2) on `dev`, or absent."""
-        import torch
-        cg, mu = _lib.CPlantGround(), cls._ground_mu(ground)
-        if mu is not None:
-            if not isinstance(mu, torch.Tensor) or mu.dtype != torch.float64 or mu.device != dev or not mu.is_contiguous() \
-                    or tuple(mu.shape) != (B, 2):
-                raise ValueError(f"ground['mu'] must be a contiguous float64 tensor on {dev} of shape {(B, 2)}")
-            cg.mu = mu.data_ptr()
-        return cg
+    def _step(self, space, B, plant, body, ground, want_applied, inputs, x_next):
+        """One plant step on exactly-typed arrays in `space` (`inputs`: x_fb, u0, foot, contact0, wrench | None): the plain entry
+        without a body and a ground, the body's without a ground, else the ground's.  Returns x_next, or with `want_applied`
+        (x_next, u_applied, flags)."""
+        args = space.ptrs(_step_rows, inputs + (x_next,), B)
+        ua = fl = None
+        if ground is None and body is None:
+            entry, structs = "bmpc_plant_step", ()
+        elif ground is None:
+            entry, structs = "bmpc_plant_step_body", (self._body(space, body, B),)
+        else:
+            entry, structs = "bmpc_plant_step_ground", (self._body(space, body, B), self._ground(space, ground, B))
+            if want_applied:
+                ua, fl = space.empty("float32", (B, 12)), space.empty("uint8", (B,))
+            args += [space.address(ua), space.address(fl)] if want_applied else [None, None]
+        _lib.check(getattr(self._lib, entry + space.suffix)(self._h, B, C.byref(plant), *structs, *args, *space.tail))
+        return (x_next, ua, fl) if want_applied else x_next
 
     def plant_step(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4, body=None, ground=None,
                    want_applied=False):
@@ -885,32 +936,11 @@ class BatchSolver:
         if a.ndim != 2 or a.shape[1] != 12:
             raise ValueError(f"x_fb must have shape (B, 12), not {a.shape}")
         B = a.shape[0]
-        arrs = [np.ascontiguousarray(a)]
-        for name, v, shp, dt in (("u0", u0, (B, 12), np.float32), ("foot", foot, (B, 6), np.float32),
-                                 ("contact0", contact0, (B, 2), None), ("wrench", wrench, (B, 6), np.float32)):
-            if v is None and name == "wrench":
-                arrs.append(None)
-                continue
-            v = np.asarray(v)
-            if v.shape != shp:
-                raise ValueError(f"{name} must have shape {shp}, not {v.shape}")
-            arrs.append(np.ascontiguousarray((v != 0).astype(np.uint8) if dt is None else v.astype(dt)))
-        out = np.empty((B, 12), np.float32)
-        if ground is not None:
-            cg, keep_g = self._ground_host(ground, B)
-            cb, keep = (None, None) if body is None else self._body_host(body, B)
-            ua, fl = (np.empty((B, 12), np.float32), np.empty(B, np.uint8)) if want_applied else (None, None)
-            _lib.check(self._lib.bmpc_plant_step_ground(self._h, B, C.byref(plant), None if cb is None else C.byref(cb), C.byref(cg),
-                                                        *[_ptr(v) for v in arrs], _ptr(out), _ptr(ua), _ptr(fl)))
-            del keep, keep_g
-            return (out.astype(np.float64), ua, fl) if want_applied else out.astype(np.float64)
-        if body is None:
-            _lib.check(self._lib.bmpc_plant_step(self._h, B, C.byref(plant), *[_ptr(v) for v in arrs], _ptr(out)))
-        else:
-            cb, keep = self._body_host(body, B)
-            _lib.check(self._lib.bmpc_plant_step_body(self._h, B, C.byref(plant), C.byref(cb), *[_ptr(v) for v in arrs], _ptr(out)))
-            del keep
-        return out.astype(np.float64)
+        inputs = (np.ascontiguousarray(a), _host_array("u0", u0, (B, 12)), _host_array("foot", foot, (B, 6)),
+                  _host_array("contact0", None if contact0 is None else np.asarray(contact0) != 0, (B, 2), np.uint8),
+                  _host_array("wrench", wrench, (B, 6), required=False))
+        res = self._step(_Host(), B, plant, body, ground, want_applied, inputs, np.empty((B, 12), np.float32))
+        return (res[0].astype(np.float64),) + res[1:] if want_applied else res.astype(np.float64)
 
     def plant_step_device(self, x_fb, u0, foot, contact0, wrench=None, integrator="rk4", substeps=4, x_next=None, stream=None,
                           body=None, ground=None, want_applied=False):
@@ -919,35 +949,15 @@ class BatchSolver:
         tensors on the device (`bmpc_plant_step_body_device`).  `ground`, `want_applied`: as for `plant_step`, mu a float64 tensor
         (B,2) on the device (`bmpc_plant_step_ground_device`); with `want_applied` the result is (x_next, u_applied (B,12) float32,
         flags (B,) uint8).  Asynchronous on `stream` (default: torch's current stream); nothing crosses PCIe."""
-        import torch
         plant = self._plant(integrator, substeps)
         self._ground_mu(ground, want_applied)
-        dev = x_fb.device
-        if dev.type != "cuda" or dev.index != self.device:
-            raise ValueError(f"tensors must live on cuda:{self.device}")
+        space = _Device(self.device, x_fb.device, stream)
         if x_fb.dim() != 2:
             raise ValueError("x_fb must have shape (B, 12)")
         B = x_fb.shape[0]
-        cb = None if body is None else self._body_device(body, B, dev)
         if x_next is None:
-            x_next = torch.empty((B, 12), dtype=torch.float32, device=dev)
-        args = [_tensor_ptr(x_fb, torch.float32, (B, 12), dev), _tensor_ptr(u0, torch.float32, (B, 12), dev),
-                _tensor_ptr(foot, torch.float32, (B, 6), dev), _tensor_ptr(contact0, torch.uint8, (B, 2), dev),
-                _tensor_ptr(wrench, torch.float32, (B, 6), dev), _tensor_ptr(x_next, torch.float32, (B, 12), dev)]
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        if ground is not None:
-            cg = self._ground_device(ground, B, dev)
-            ua = torch.empty((B, 12), dtype=torch.float32, device=dev) if want_applied else None
-            fl = torch.empty((B,), dtype=torch.uint8, device=dev) if want_applied else None
-            _lib.check(self._lib.bmpc_plant_step_ground_device(
-                self._h, B, C.byref(plant), None if cb is None else C.byref(cb), C.byref(cg), *args,
-                None if ua is None else ua.data_ptr(), None if fl is None else fl.data_ptr(), st))
-            return (x_next, ua, fl) if want_applied else x_next
-        if cb is None:
-            _lib.check(self._lib.bmpc_plant_step_device(self._h, B, C.byref(plant), *args, st))
-        else:
-            _lib.check(self._lib.bmpc_plant_step_body_device(self._h, B, C.byref(plant), C.byref(cb), *args, st))
-        return x_next
+            x_next = space.empty("float32", (B, 12))
+        return self._step(space, B, plant, body, ground, want_applied, (x_fb, u0, foot, contact0, wrench), x_next)
 
     def simulate_device(self, x_fb, foot, t, steps, x_cmd=None, mu=None, period=None, offset=None, duty=None, integrator="rk4",
                         substeps=4, move_feet=True, push=None, push_from=0, push_steps=0, want_iters=True, stream=None, body=None,
@@ -973,38 +983,28 @@ class BatchSolver:
         import torch
         plant = self._plant(integrator, substeps, move_feet, push_from, push_steps)
         self._ground_mu(ground)
-        if ground is not None and not float(fz_floor) >= 0.0:
-            raise ValueError("fz_floor must be >= 0 and not NaN")
+        floor = None if ground is None else _fz_floor(fz_floor)
         if fall is not None:
-            try:
-                tilt_max, z_min = (float(v) for v in fall)
-            except (TypeError, ValueError):
-                raise ValueError("fall must be a (tilt_max, z_min) pair") from None
-            if tilt_max != tilt_max or z_min != z_min:
-                raise ValueError("fall thresholds must not be NaN")
-        dev = x_fb.device
-        if dev.type != "cuda" or dev.index != self.device:
-            raise ValueError(f"tensors must live on cuda:{self.device}")
+            tilt_max, z_min = _fall(fall)
+        space = _Device(self.device, x_fb.device, stream)
+        dev = space.dev
         if x_fb.dim() != 2 or int(steps) < 0:
             raise ValueError("x_fb must have shape (B, 12) and steps must be >= 0")
         B, steps = x_fb.shape[0], int(steps)
-        cb = None if body is None else self._body_device(body, B, dev)
-        args = [_tensor_ptr(x_fb, torch.float32, (B, 12), dev), _tensor_ptr(foot, torch.float32, (B, 6), dev),
-                _tensor_ptr(t, torch.float64, (B,), dev)]
-        opt = [_tensor_ptr(x_cmd, torch.float32, (B, 12), dev), _tensor_ptr(mu, torch.float32, (B, self.h, 2), dev),
-               _tensor_ptr(push, torch.float32, (B, 6), dev)]
+        cb = self._body(space, body, B)
+        a = space.ptrs(_loop_rows, (x_fb, foot, t, x_cmd, mu, push), B, self.h)
+        args, opt = a[:3], a[3:]
         gait = self._gait(period, offset, duty)
         u0 = torch.empty((steps, B, 12), dtype=torch.float32, device=dev)
         xt = torch.empty((steps, B, 12), dtype=torch.float32, device=dev)
         ft = torch.empty((steps, B, 6), dtype=torch.float32, device=dev)
         its = torch.empty((steps, B), dtype=torch.int32, device=dev) if want_iters else None
         st_any = torch.zeros(B, dtype=torch.int32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
         out = dict(u0=u0, x=xt, foot=ft, iters=its, status_any=st_any)
         traj = [u0.data_ptr(), xt.data_ptr(), ft.data_ptr(), None if its is None else its.data_ptr(), st_any.data_ptr()]
         if cb is None and fall is None and ground is None:
             _lib.check(self._lib.bmpc_simulate_device(
-                self._h, B, steps, C.byref(plant), *args, None if gait is None else C.byref(gait), *opt, *traj, st))
+                self._h, B, steps, C.byref(plant), *args, None if gait is None else C.byref(gait), *opt, *traj, *space.tail))
             return out
         co = None
         if fall is not None:
@@ -1014,7 +1014,6 @@ class BatchSolver:
                        min_z=torch.full((B,), float("nan"), dtype=torch.float32, device=dev))
             co = _lib.CSimOutcome(tilt_max, z_min, out["first_fall"].data_ptr(), out["max_tilt"].data_ptr(), out["min_z"].data_ptr())
         if ground is not None:
-            cg = self._ground_device(ground, B, dev)
             # (the reduced arrays filled here as the entry does it, like the outcome's)
             out.update(u_applied=torch.empty((steps, B, 12), dtype=torch.float32, device=dev),
                        contact_flags=torch.empty((steps, B), dtype=torch.uint8, device=dev),
@@ -1022,15 +1021,15 @@ class BatchSolver:
                        slip_periods=torch.zeros((B, 2), dtype=torch.int32, device=dev),
                        unloaded_periods=torch.zeros((B, 2), dtype=torch.int32, device=dev),
                        mu_demand=torch.full((B,), float("nan"), dtype=torch.float32, device=dev))
-            go = _lib.CGroundOut(float(fz_floor), *[out[k].data_ptr() for k in ("u_applied", "contact_flags", "first_slip", "slip_periods",
+            go = _lib.CGroundOut(floor, *[out[k].data_ptr() for k in ("u_applied", "contact_flags", "first_slip", "slip_periods",
                                                                                 "unloaded_periods", "mu_demand")])
             _lib.check(self._lib.bmpc_simulate_ground_device(
-                self._h, B, steps, C.byref(plant), None if cb is None else C.byref(cb), C.byref(cg), *args,
-                None if gait is None else C.byref(gait), *opt, *traj, None if co is None else C.byref(co), C.byref(go), st))
+                self._h, B, steps, C.byref(plant), cb, self._ground(space, ground, B), *args,
+                None if gait is None else C.byref(gait), *opt, *traj, None if co is None else C.byref(co), C.byref(go), *space.tail))
             return out
         _lib.check(self._lib.bmpc_simulate_body_device(
-            self._h, B, steps, C.byref(plant), None if cb is None else C.byref(cb), *args, None if gait is None else C.byref(gait), *opt,
-            *traj, None if co is None else C.byref(co), st))
+            self._h, B, steps, C.byref(plant), cb, *args, None if gait is None else C.byref(gait), *opt,
+            *traj, None if co is None else C.byref(co), *space.tail))
         return out
 
     # ---- S candidate plans per instance on the plant (bmpc_plant_rollout_samples*) ---------------------
@@ -1053,17 +1052,7 @@ class BatchSolver:
         w = [float(v) for v in (w_fall, w_slip, w_unloaded)]
         if not all(np.isfinite(v) and v >= 0.0 for v in w):
             raise ValueError("w_fall, w_slip and w_unloaded must be finite and >= 0")
-        T = float(temperature)
-        if not T > 0.0:
-            raise ValueError("temperature must be > 0 (inf: uniform weights)")
-        try:
-            tilt_max, z_min = (float(v) for v in fall)
-        except (TypeError, ValueError):
-            raise ValueError("fall must be a (tilt_max, z_min) pair") from None
-        if tilt_max != tilt_max or z_min != z_min:
-            raise ValueError("fall thresholds must not be NaN")
-        if not float(fz_floor) >= 0.0:
-            raise ValueError("fz_floor must be >= 0 and not NaN")
+        T, (tilt_max, z_min), floor = _temperature(temperature), _fall(fall), _fz_floor(fz_floor)
         names = [k for k, _, _ in cls._ROLLOUT_OUTPUTS]
         if want is None:
             want = [k for k in names if ground is not None or k not in cls._ROLLOUT_GROUND_ONLY]
@@ -1074,7 +1063,21 @@ class BatchSolver:
             raise ValueError(f"{', '.join(cls._ROLLOUT_GROUND_ONLY)} need a ground")
         if not 1 <= int(S) <= SAMPLES_MAX:
             raise ValueError(f"controls must hold 1 <= S <= {SAMPLES_MAX} plans per instance")
-        return plant, _lib.CRolloutPrice(int(S), 0, *w, T, tilt_max, z_min, float(fz_floor)), want
+        return plant, _lib.CRolloutPrice(int(S), 0, *w, T, tilt_max, z_min, floor), want
+
+    def _rollout(self, space, B, S, opts, inputs, body, ground):
+        """The plan roll-out on exactly-typed arrays in `space`: `opts` as `_rollout_opts` returns them, `inputs` in the order of
+        `_rollout_input_rows`.  The wanted outputs are allocated here; one call; returns their dict."""
+        plant, price, want = opts
+        args = space.ptrs(_rollout_input_rows, inputs, B, self.h, S)
+        cb, cg = self._body(space, body, B), self._ground(space, ground, B)
+        res = {k: space.empty(dtype, _shape(shape, B, self.h, S)) for k, dtype, shape in self._ROLLOUT_OUTPUTS if k in want}
+        out = _lib.CRolloutOut(**{k: space.address(a) for k, a in res.items()})
+        if B == 0 and space.empty_is_null:      # (nothing to do, and an empty tensor has no address to hand over)
+            return res
+        _lib.check(getattr(self._lib, "bmpc_plant_rollout_samples" + space.suffix)(
+            self._h, B, *args, C.byref(plant), cb, cg, C.byref(price), C.byref(out), *space.tail))
+        return res
 
     def plant_rollout_samples(self, x_fb, foot, contact, controls, x_cmd=None, x_ref=None, push=None, push_from=0, push_steps=0,
                               integrator="rk4", substeps=4, move_feet=True, body=None, ground=None, fall=(float("inf"), float("-inf")),
@@ -1097,30 +1100,12 @@ class BatchSolver:
         every plan of it so."""
         c32 = _samples_f32(controls, self.h)
         B, S, h = c32.shape[0], c32.shape[1], self.h
-        plant, price, want = self._rollout_opts(S, push_from, push_steps, integrator, substeps, move_feet, ground, fall, fz_floor,
-                                                w_fall, w_slip, w_unloaded, temperature, want)
-        arrs = []
-        for name, v, shp in (("x_fb", x_fb, (B, 12)), ("foot", foot, (B, 6)), ("x_cmd", x_cmd, (B, 12)), ("x_ref", x_ref, (B, h, 12)),
-                             ("push", push, (B, 6))):
-            if v is not None:
-                v = np.asarray(v)
-                if v.shape != shp:
-                    raise ValueError(f"{name} must have shape {shp}, not {v.shape}")
-                v = np.ascontiguousarray(v, np.float32)
-            elif name in ("x_fb", "foot"):
-                raise ValueError(f"{name} is required")
-            arrs.append(v)
-        xf, ft, xc, xr, ps = arrs
-        con = _contact_u8(contact, B, h)
-        cb, keep = (None, None) if body is None else self._body_host(body, B)
-        cg, keep_g = (None, None) if ground is None else self._ground_host(ground, B)
-        res = {k: np.empty(_shape(shp, B, h, S), dt) for k, dt, shp in self._ROLLOUT_OUTPUTS if k in want}
-        out = _lib.CRolloutOut(**{k: _ptr(v) for k, v in res.items()})
-        _lib.check(self._lib.bmpc_plant_rollout_samples(
-            self._h, B, _ptr(xf), _ptr(ft), _ptr(con), _ptr(xc), _ptr(xr), _ptr(ps), _ptr(c32), C.byref(plant),
-            None if cb is None else C.byref(cb), None if cg is None else C.byref(cg), C.byref(price), C.byref(out)))
-        del keep, keep_g
-        return res
+        opts = self._rollout_opts(S, push_from, push_steps, integrator, substeps, move_feet, ground, fall, fz_floor, w_fall, w_slip,
+                                  w_unloaded, temperature, want)
+        inputs = (_host_array("x_fb", x_fb, (B, 12)), _host_array("foot", foot, (B, 6)), _contact_u8(contact, B, h),
+                  _host_array("x_cmd", x_cmd, (B, 12), required=False), _host_array("x_ref", x_ref, (B, h, 12), required=False),
+                  _host_array("push", push, (B, 6), required=False), c32)
+        return self._rollout(_Host(), B, S, opts, inputs, body, ground)
 
     def plant_rollout_samples_device(self, x_fb, foot, contact, controls, x_cmd=None, x_ref=None, push=None, push_from=0, push_steps=0,
                                      integrator="rk4", substeps=4, move_feet=True, body=None, ground=None,
@@ -1132,32 +1117,13 @@ class BatchSolver:
         allocated here; one launch, and a second for the per-instance reductions where one of them is wanted.  Asynchronous on
         `stream` (default: torch's current stream) unless the handle's scratch has to grow (include/bmpc.h); nothing crosses PCIe.
         Returns the dict of output tensors."""
-        import torch
-        h = self.h
         if x_fb.dim() != 2 or controls.dim() != 4:
-            raise ValueError(f"x_fb must have shape (B, 12) and controls (B, S, {h}, 12)")
+            raise ValueError(f"x_fb must have shape (B, 12) and controls (B, S, {self.h}, 12)")
         B, S = x_fb.shape[0], int(controls.shape[1])
-        plant, price, want = self._rollout_opts(S, push_from, push_steps, integrator, substeps, move_feet, ground, fall, fz_floor,
-                                                w_fall, w_slip, w_unloaded, temperature, want)
-        dev = x_fb.device
-        if dev.type != "cuda" or dev.index != self.device:
-            raise ValueError(f"tensors must live on cuda:{self.device}")
-        args = [_tensor_ptr(t, dt, shp, dev) for t, dt, shp in (
-            (x_fb, torch.float32, (B, 12)), (foot, torch.float32, (B, 6)), (contact, torch.uint8, (B, h, 2)),
-            (x_cmd, torch.float32, (B, 12)), (x_ref, torch.float32, (B, h, 12)), (push, torch.float32, (B, 6)),
-            (controls, torch.float32, (B, S, h, 12)))]
-        cb = None if body is None else self._body_device(body, B, dev)
-        cg = None if ground is None else self._ground_device(ground, B, dev)
-        res = {k: torch.empty(_shape(shp, B, h, S), dtype=getattr(torch, dt), device=dev) for k, dt, shp in self._ROLLOUT_OUTPUTS
-               if k in want}
-        if B == 0:                                       # (nothing to do, and an empty tensor has no address to hand over)
-            return res
-        out = _lib.CRolloutOut(**{k: v.data_ptr() for k, v in res.items()})
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        _lib.check(self._lib.bmpc_plant_rollout_samples_device(
-            self._h, B, *args, C.byref(plant), None if cb is None else C.byref(cb), None if cg is None else C.byref(cg), C.byref(price),
-            C.byref(out), st))
-        return res
+        opts = self._rollout_opts(S, push_from, push_steps, integrator, substeps, move_feet, ground, fall, fz_floor, w_fall, w_slip,
+                                  w_unloaded, temperature, want)
+        return self._rollout(_Device(self.device, x_fb.device, stream), B, S, opts, (x_fb, foot, contact, x_cmd, x_ref, push, controls),
+                             body, ground)
 
     def last_kernel_ms(self):
         ms = C.c_float(-1.0)
@@ -1207,6 +1173,17 @@ def _cached_solver(mpc, biped, half, device, solver_options):
     return s
 
 
+def _mpc_or_default(mpc):
+    return mpc if mpc is not None else MPC()
+
+
+def _solver_and_phase(mpc, biped, half, device, solver_options, t, phase):
+    """What every batch wrapper ends its preamble with, AFTER its checks (which need `_mpc_or_default(mpc).h` and must come before
+    a solver handle can be created): the cached solver, and the phase from `t` unless it was given."""
+    solver = _cached_solver(mpc, biped, half, device, solver_options)
+    return solver, phase_indices(t, mpc.dt, mpc.h) if phase is None else phase
+
+
 def close_cached_solvers():
     """Destroy the handles the drop-in wrappers keep (tests; orderly shutdown)."""
     for s in _SOLVERS.values():
@@ -1219,16 +1196,11 @@ def _batch_call(controls, t, mpc, biped, half, device, phase, x_ref, foot_ref, a
     evaluation takes them, the references from the reference's orientation to the kernel layout, a NaN `act_tol` refused (the
     certificate's; the others leave the default), the cached solver, the phase from `t`.  Every check comes before a solver handle
     can be created.  Returns (solver, phase, x_ref, foot_ref, controls)."""
-    from .params import MPC
-    mpc = mpc if mpc is not None else MPC()
+    mpc = _mpc_or_default(mpc)
     c32 = _controls_f32(controls, int(mpc.h))
     xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
-    if float(act_tol) != float(act_tol):
-        raise ValueError("act_tol must not be NaN")
-    solver = _cached_solver(mpc, biped, half, device, None)
-    if phase is None:
-        phase = phase_indices(t, mpc.dt, mpc.h)
-    return solver, phase, xr, fr, c32
+    _act_tol(act_tol)
+    return _solver_and_phase(mpc, biped, half, device, None, t, phase) + (xr, fr, c32)
 
 
 def _contact_rows(contact, h):
@@ -1260,12 +1232,9 @@ def solve_mpc_batch(x_fb, t, foot, contact, mpc=None, biped=None, x_cmd=None, mu
     foot_ref (B,6,h) -- what `reference_trajectories_batch` returns, so "generate, edit, pass back" works.
     Returns states (B,h,13), controls (B,h,12) [, info].  Without `return_info` a NaN/Inf instance raises
     FloatingPointError and instances stopped at the iteration cap raise a SolverStatusWarning."""
-    from .params import MPC
-    mpc = mpc if mpc is not None else MPC()
+    mpc = _mpc_or_default(mpc)
     xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
-    solver = _cached_solver(mpc, biped, half, device, solver_options)
-    if phase is None:
-        phase = phase_indices(t, mpc.dt, mpc.h)
+    solver, phase = _solver_and_phase(mpc, biped, half, device, solver_options, t, phase)
     states, controls, info = solver.solve(x_fb, foot, contact, phase, x_cmd=x_cmd, mu=mu, x_ref=xr, foot_ref=fr)
     if return_info:
         return states, controls, info
@@ -1311,14 +1280,11 @@ def evaluate_samples_mpc_batch(x_fb, t, foot, contact, controls, mpc=None, biped
     orientation, the cached handle per horizon and device) with `controls` (B,S,h,12), the prices `w_viol` of the four violation
     classes and the `temperature` of the softmin weights.  Returns the dict of `BatchSolver.evaluate_samples`.  Every check comes
     before a solver handle can be created."""
-    from .params import MPC
-    mpc = mpc if mpc is not None else MPC()
+    mpc = _mpc_or_default(mpc)
     c32 = _samples_f32(controls, int(mpc.h))
     _samples_desc(c32.shape[1], w_viol, temperature)
     xr, fr = references_to_kernel_layout(x_ref, foot_ref, int(mpc.h))
-    solver = _cached_solver(mpc, biped, half, device, None)
-    if phase is None:
-        phase = phase_indices(t, mpc.dt, mpc.h)
+    solver, phase = _solver_and_phase(mpc, biped, half, device, None, t, phase)
     return solver.evaluate_samples(x_fb, foot, contact, phase, c32, x_cmd=x_cmd, mu=mu, x_ref=xr, foot_ref=fr, w_viol=w_viol,
                                    temperature=temperature)
 
@@ -1361,12 +1327,9 @@ def certify_mpc(x_fb, t, foot, mpc, biped, contact, controls, half=None, device=
 def reference_trajectories_batch(x_fb, t, foot, contact, mpc=None, biped=None, x_cmd=None, phase=None, half=None, device=0):
     """Batched REF:61-109 on the device (the generators phase 1 of the solve kernel runs, exposed through
     `bmpc_debug_assemble`): x_ref (B,13,h) and foot_ref (B,6,h), fp64, in the reference's row/column order."""
-    from .params import MPC
-    mpc = mpc if mpc is not None else MPC()
-    solver = _cached_solver(mpc, biped, half, device, None)
+    mpc = _mpc_or_default(mpc)
+    solver, phase = _solver_and_phase(mpc, biped, half, device, None, t, phase)
     x_fb = np.asarray(x_fb, float).reshape(-1, 12)
-    if phase is None:
-        phase = phase_indices(t, mpc.dt, mpc.h)
     x_ref, foot_ref, _, _ = solver.assemble(x_fb, foot, contact, phase, x_cmd=x_cmd, want_matrices=False)
     B, h = x_ref.shape[0], x_ref.shape[1]
     xr = np.concatenate([x_ref.transpose(0, 2, 1), np.ones((B, 1, h))], axis=1)       # REF:62: 13th row of ones
@@ -1394,8 +1357,7 @@ def get_reference_foot_trajectory(x_fb, t, foot, mpc, contact, half=None, device
 
 def getFootPositionWorld(x_fb, q, biped, mpc=None, device=0):
     """Drop-in for REF:406-424: returns pf_w (6,1) fp64 like the reference."""
-    from .params import MPC
-    solver = _cached_solver(mpc if mpc is not None else MPC(), biped, None, device, None)
+    solver = _cached_solver(_mpc_or_default(mpc), biped, None, device, None)
     return solver.foot_position_world(np.asarray(x_fb, float).reshape(1, 12), np.asarray(q, float).reshape(1, 10)).reshape(6, 1)
 
 
