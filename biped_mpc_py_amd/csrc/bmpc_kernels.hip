@@ -41,6 +41,7 @@
 namespace bmpc {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
+typedef float f4 __attribute__((ext_vector_type(4)));
 
 #ifndef BMPC_EMU
 __device__ __forceinline__ double rcp_approx(double x) { return __builtin_amdgcn_rcp(x); }
@@ -48,6 +49,14 @@ __device__ __forceinline__ float rcp_approx(float x) { return __builtin_amdgcn_r
 __device__ __forceinline__ float rsq_approx(float x) { return __builtin_amdgcn_rsqf(x); }
 // value of the other lane of the pair (lane ^ 1): DPP quad_perm [1, 0, 3, 2].  Call with all lanes active.
 __device__ __forceinline__ int pair_swap_i(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false); }
+// value of the lane two over in the aligned quad (lane ^ 2): DPP quad_perm [2, 3, 0, 1].  Call with all lanes active.
+// (every lane has a source, so no `old` value has to be set up: the move folds into the instruction that uses it)
+__device__ __forceinline__ int quad_swap_i(int v) { return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true); }
+// The last quad of a wave (lanes 60 .. 63: the clone lanes where five steps fill a wave) takes the value of the quad below it
+// (row_shr:4, written in row 3 / bank 3 only) -- or its first lane pair that of its second (quad_perm [2, 3, 2, 3]); every
+// other lane keeps v.  Call with all lanes active.
+__device__ __forceinline__ int tail_quad_fill_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x114, 0x8, 0x8, false); }
+__device__ __forceinline__ int tail_pair_fill_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0xEE, 0x8, 0x8, false); }
 // Workgroup barrier.  __syncthreads() alone is not enough here: its release fence should make the compiler wait for
 // the wave's outstanding LDS operations (s_waitcnt lgkmcnt(0)) before s_barrier, but ROCm 7.2's hipcc leaves that
 // wait out at the top of the sweep loop, whose back edge carries a pending ds_write (the publication of the next
@@ -79,10 +88,20 @@ __device__ __forceinline__ int sync_workgroup_or(int v) {
 // hides a loop-invariant f32 value from the optimiser at its point of use, so that its f64 conversion is
 // redone there instead of being hoisted into a second, f64, register copy that lives across the loop
 #define BMPC_OPAQUE(x) asm volatile("" : "+v"(x))
+// makes a 64-bit half of a wider register tuple a value of its own: the packed-f32 operand selection (op_sel) then broadcasts its
+// upper element in place, where the compiler copies element 3 of a 128-bit tuple into a fresh register first
+#define BMPC_PAIR(x) asm("" : "+v"(x))
 // a condition every lane of the wave evaluates alike, as a scalar (the branch on it is a scalar branch)
 #define BMPC_UNIFORM(x) (__builtin_amdgcn_readfirstlane((int)(x)) != 0)
 // an integer every lane of the wave computes alike, as a scalar (loop bounds on it make a scalar loop)
 #define BMPC_UNIFORM_INT(x) __builtin_amdgcn_readfirstlane((int)(x))
+#else
+// tests/emu: the quad exchange and the tail fills of the row-pair sweep, on the emulation's wave-wide permute (lane_read:
+// every lane of the wave calls, a shared array between two barriers of the wave)
+static inline int quad_swap_i(int v) { return lane_read(v, (int)(threadIdx.x & 63) ^ 2); }
+static inline int tail_quad_fill_i(int v) { const int ln = threadIdx.x & 63; return lane_read(v, ln >= 60 ? ln - 4 : ln); }
+static inline int tail_pair_fill_i(int v) { const int ln = threadIdx.x & 63; return lane_read(v, ln == 60 || ln == 61 ? ln + 2 : ln); }
+#define BMPC_PAIR(x) do { } while (0)
 #endif
 __device__ __forceinline__ double widen(float v) { BMPC_OPAQUE(v); return (double)v; }
 __device__ __forceinline__ float pair_swap(float v) { return __int_as_float(pair_swap_i(__float_as_int(v))); }
@@ -91,6 +110,9 @@ __device__ __forceinline__ double pair_swap(double v) {
   return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ f2 pair_swap(f2 v) { return f2{pair_swap(v.x), pair_swap(v.y)}; }
+__device__ __forceinline__ float quad_swap(float v) { return __int_as_float(quad_swap_i(__float_as_int(v))); }
+__device__ __forceinline__ float tail_quad_fill(float v) { return __int_as_float(tail_quad_fill_i(__float_as_int(v))); }
+__device__ __forceinline__ float tail_pair_fill(float v) { return __int_as_float(tail_pair_fill_i(__float_as_int(v))); }
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 #ifndef BMPC_EMU
@@ -1249,7 +1271,10 @@ solve_body(const DevParams& P, const int B,
     // it) on the matrix + PIV_REG I (added to the diagonal before the scaling): its pivots are then >= PIV_REG, and since the inverse only preconditions the residual
     // form (section 3) the regularisation costs that factorisation some convergence rate in the softest directions, never
     // the fixed point.  At the reference's weights no instance of the soaks takes the second pass.
-    constexpr float PIV_MIN = 2.0e-6f;
+#ifndef BMPC_PIV_MIN
+#define BMPC_PIV_MIN 2.0e-6f                  // (tests/emu raises it to send every factorisation through the repeat)
+#endif
+    constexpr float PIV_MIN = BMPC_PIV_MIN;
 #pragma unroll
     for (int q = 0; q < HN; ++q) {
       const int jj = q / 6, b = q % 6;
@@ -1305,7 +1330,159 @@ solve_body(const DevParams& P, const int B,
 #define BMPC_STATIC_HN 54
 #endif
     constexpr bool STATIC_SWEEP = HN <= BMPC_STATIC_HN;
-    if constexpr (STATIC_SWEEP) {
+    // The row-pair form of the static sweep (round 24).  Above, a lane fetches the HN entries of both pivot rows of its column
+    // half and every fetched entry feeds ONE FMA: 14 ds_read_b128 a step at h = 10, all of them broadcasts, and a broadcast costs
+    // the LDS array what 64 distinct addresses cost -- the array, not the vector port, is the busier of the two resources the
+    // four resident instances share.  Here the four lanes of an aligned quad (rows rA = 2 m and rA + 1,
+    // halves 0 and 1) hold HN / 2 columns of BOTH rows for the duration of the sweep: lane (hf, p = (l >> 1) & 1) the columns of
+    // parity p of half hf, register pair i = {V[rA][c], V[rA + 1][c]}, c = hf HN + 2 i + p -- packed across the two rows, so a
+    // fetched pivot-row entry feeds both halves of a packed FMA (the compiler broadcasts it with op_sel) and the pivot-row
+    // traffic halves: 8 ds_read_b128 a step.  Every entry of V sees the same two FMAs with the same operands in the same
+    // order as above; the pivot algebra, the pivot check and the multipliers (per row, mul then fma) are those of above too:
+    // results identical to the bit.
+    //   * Columns by parity, not by contiguous quarters: the two pivot columns of a step then always sit in register u / 2
+    //     of the two lanes of a half (no step straddles two lanes, every register index is static), each lane publishes the
+    //     two rows' entries of ONE column with one ds_write2_b32, and no lane needs the other's entries for it.
+    //   * A published column is laid out as it is read: 4 quarters (half, parity) of QP floats (HN / 2 entries + padding to
+    //     whole float4s; the padding is never written and never used), so the entries of rows rA, rA + 1 lie QP apart -- the
+    //     store's two static offsets -- and a lane's part of a pivot row is QP / 4 aligned float4s.
+    //   * In and out: the 2 x 2 transposition between lanes l and l ^ 2 (DPP quad_perm, 2 moves + 2 selects per register pair).
+    //     Values are moved, never recomputed.  The clone lanes (60 .. 63 of a wave) become a copy of the quad below them, rows
+    //     28, 29 of the wave, for the sweep, so that their stores repeat real lanes' values at those lanes' addresses, and are
+    //     turned back into clones of the wave's last row behind it (one DPP move per register each way).
+    // Selected for HN <= BMPC_ROWPAIR_HN (0: the form above for every horizon, the code of round 23 instruction for instruction)
+    // where five steps fill a wave (the clone quad above) and the quarters fit the two-half vector: h = 10.
+#ifndef BMPC_ROWPAIR_HN
+#define BMPC_ROWPAIR_HN 30
+#endif
+    constexpr int QP = ((HN / 2 + 3) / 4) * 4;   // floats per quarter of a published column
+    constexpr bool ROWPAIR_SWEEP = STATIC_SWEEP && HN <= BMPC_ROWPAIR_HN && Dims<H>::WL && 4 * QP <= Dims<H>::VL &&
+                                   Dims<H>::VL + 32 + QP <= PVS;
+    if constexpr (ROWPAIR_SWEEP) {
+      const int p = (l >> 1) & 1;                // column parity held in the sweep
+      auto quad_transpose = [&]() {              // {row, 2 columns} <-> {2 rows, column}: its own inverse
+#pragma unroll
+        for (int i = 0; i < HN / 2; ++i) {
+          const float ox = quad_swap(Vr[i].x), oy = quad_swap(Vr[i].y);
+          Vr[i] = p ? f2{oy, Vr[i].y} : f2{Vr[i].x, ox};
+        }
+      };
+      quad_transpose();
+#pragma unroll
+      for (int i = 0; i < HN / 2; ++i) Vr[i] = f2{tail_quad_fill(Vr[i].x), tail_quad_fill(Vr[i].y)};
+      const int rA = row & ~1;                   // first row of the quad (clone lanes: of the quad they copy)
+      const int hA = rA >= HN ? 1 : 0;
+      const int sA = hA * 2 * QP + ((rA - hA * HN) >> 1);   // its entry in a published column; row rA + 1: QP further
+      const int qb = (2 * hf + p) * QP;          // the own quarter
+      const int wpub = p * PVS + sA;             // publication slot (parity p: the second column of the step)
+      const int wdump = p * PVS + Dims<H>::VL + ((l & 63) >> 1);   // where the lanes of the other half store instead
+      // LDS accesses of the sweep go through byte offsets into the two pivot buffers that are formed -- and pinned in registers --
+      // at the top of a column half, in front of its first barrier: a half has an odd number of steps at h = 10, so which buffer
+      // a step reads alternates from half to half, and address arithmetic left to the compiler lands behind the first barrier
+      char* const pvb = reinterpret_cast<char*>(&sm.piv[0][0]);
+      constexpr int BUFB = 2 * PVS * 4, COLB = PVS * 4, QB = QP * 4;   // bytes: a buffer, a column, a quarter
+      auto ldf = [&](int b) { return *reinterpret_cast<const float*>(pvb + b); };
+      auto ld4 = [&](int b) { return *reinterpret_cast<const f4*>(pvb + b); };
+      auto stf = [&](int b, float v) { *reinterpret_cast<float*>(pvb + b) = v; };
+      {
+        const int ws0 = 4 * (hf == 0 ? wpub : wdump);
+        stf(ws0, Vr[0].x);
+        stf(ws0 + QB, Vr[0].y);
+      }
+#pragma unroll 1
+      for (int hh = 0; hh < 2; ++hh) {           // the column half that holds the pivots
+        const int wsh = hf == hh ? wpub : wdump;                        // publication slot while this half publishes (else: dump)
+        const int wso = hf == hh + 1 ? wpub : wdump;                    // ... and for the first pivots of the next half
+        const int kb = hh * HN;                   // first pivot of the half
+        const int pb0 = hh * 2 * QP;              // its slot
+        const int par0 = (HN / 2) % 2 ? hh : 0;   // buffer of the half's first step
+        constexpr int XL = (HN / 2 - 1) & 1;      // the half's last step reads buffer par0 ^ XL
+        int bufb[2] = {par0 * BUFB, (par0 ^ 1) * BUFB};
+        int rq[2], rc[2], rp[2], wp[2];           // [step parity]: own quarter, own rows' entries, pivot block; publication of the NEXT step
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+          rq[x] = bufb[x] + 4 * qb;
+          rc[x] = bufb[x] + 4 * sA;
+          rp[x] = bufb[x] + 4 * pb0;
+          wp[x] = bufb[x ^ 1] + 4 * wsh;
+          BMPC_OPAQUE(rq[x]); BMPC_OPAQUE(rc[x]); BMPC_OPAQUE(rp[x]); BMPC_OPAQUE(wp[x]);
+        }
+        int wl = bufb[XL ^ 1] + 4 * wso;
+        BMPC_OPAQUE(wl);
+#pragma unroll
+        for (int u = 0; u < HN; u += 2) {
+          const int X = (u >> 1) & 1;                      // the step reads buffer par0 ^ X (columns k = kb + u, k + 1), writes the other
+          const int un = u + 2 < HN ? (u >> 1) + 1 : 0;  // register pair of the next pivot column (last step of a half: the other half's first)
+          constexpr int NQ = QP / 4;
+          const int jn = un / 4;                           // the float4 with the next pivot column's entries: fetched first
+          f4 a4[NQ], b4[NQ];
+          auto bc = [](const f4& v, int k) -> f2 {         // entry k to both halves of the packed operand (op_sel)
+            if (k == 3) { f2 hi = v.zw; BMPC_PAIR(hi); return hi.yy; }
+            return k == 0 ? v.xx : (k == 1 ? v.yy : v.zz);
+          };
+          BMPC_SCHED_BARRIER();                            // (no FMA of the step before sinks behind the barrier)
+          sync_workgroup();
+          const float pkx = ldf(rp[X] + 2 * u), pky = ldf(rp[X] + 2 * u + QB);   // V[k][k], V[k + 1][k]
+          const float p11 = ldf(rp[X] + COLB + 2 * u + QB);
+          const float c0A = ldf(rc[X]), c1A = ldf(rc[X] + COLB);            // V[rA][k], V[rA][k + 1]
+          const float c0B = ldf(rc[X] + QB), c1B = ldf(rc[X] + COLB + QB);  // V[rA + 1][k], V[rA + 1][k + 1]
+          // the own part of both pivot rows goes out at the barrier too, behind the scalars (round 7): its latency runs
+          // under the pivot algebra below, which needs none of it
+          a4[jn] = ld4(rq[X] + 16 * jn);
+          b4[jn] = ld4(rq[X] + COLB + 16 * jn);
+          BMPC_SCHED_BARRIER();                            // (LDS returns in order: the publication waits for these alone)
+#pragma unroll
+          for (int jq = 0; jq < NQ; ++jq)
+            if (jq != jn) {
+              a4[jq] = ld4(rq[X] + 16 * jq);
+              b4[jq] = ld4(rq[X] + COLB + 16 * jq);
+            }
+          BMPC_SCHED_BARRIER();                            // the step's loads are in flight before anything is used
+          const float id = rcp_approx(pkx * p11 - pky * pky);
+          const float q00 = p11 * id, q01 = -pky * id, q11 = pkx * id;    // P^-1
+          qmax = fmaxf(qmax, fmaxf(q00, q11));             // (pivot check: see the rotating form)
+          qmin = fminf(qmin, fminf(q00, q11));
+          const bool isp = (rA == kb + u);                 // the quad's rows are the pivot rows k, k + 1
+          const float tA0 = c0A * q00 + c1A * q01, tA1 = c0A * q01 + c1A * q11;
+          const float tB0 = c0B * q00 + c1B * q01, tB1 = c0B * q01 + c1B * q11;
+          // (the negated multipliers: q - 1 is 1 - q negated to the bit, and the selects take the other negations along)
+          const f2 m0 = {isp ? q00 - 1.f : -tA0, isp ? q01 : -tB0};
+          const f2 m1 = {isp ? q01 : -tA1, isp ? q11 - 1.f : -tB1};
+          auto keep_pad = [&]() {                          // the padding is fetched with the rest: a 16-byte read costs the LDS
+            if constexpr (HN / 2 % 4 != 0) {               // array half of what the 12-byte read costs that the compiler would
+              BMPC_OPAQUE(a4[NQ - 1]);                     // shrink it to (placed at the vector's first use: the wait is the same)
+              BMPC_OPAQUE(b4[NQ - 1]);
+            }
+          };
+          auto upd = [&](int r) {
+            Vr[r] = __builtin_elementwise_fma(m1, bc(b4[r / 4], r % 4), __builtin_elementwise_fma(m0, bc(a4[r / 4], r % 4), Vr[r]));
+          };
+          // the next pivot column first, published at once, the scheduling barrier behind the store (see the form below)
+          {
+            if (jn == NQ - 1) keep_pad();
+            upd(un);
+            const int wn = u + 2 < HN ? wp[X] : wl;        // (after the very last step: columns nobody reads)
+            stf(wn, Vr[un].x);
+            stf(wn + QB, Vr[un].y);
+          }
+          BMPC_SCHED_BARRIER();
+#pragma unroll
+          for (int r = 0; r < HN / 2; ++r) {
+            if (r == 4 * (NQ - 1) && jn != NQ - 1) keep_pad();
+            if (r != un) upd(r);
+          }
+          if (hf == hh) {                          // column k (p = 0) / k + 1 (p = 1) becomes T, in the pivot block -P^-1
+            const float xA0 = isp ? -q00 : tA0, xA1 = isp ? -q01 : tA1;   // (the selects take the negations along)
+            const float xB0 = isp ? -q01 : tB0, xB1 = isp ? -q11 : tB1;
+            Vr[u >> 1] = p ? f2{xA1, xB1} : f2{xA0, xB0};
+          }
+        }
+        BMPC_DRAIN_LDS();                         // nothing in flight across the back edge (see sync_workgroup)
+      }
+      quad_transpose();
+#pragma unroll
+      for (int i = 0; i < HN / 2; ++i) Vr[i] = f2{tail_pair_fill(Vr[i].x), tail_pair_fill(Vr[i].y)};
+    } else if constexpr (STATIC_SWEEP) {
       const int ps = slot<H>(row);              // the own row's entry in a published column
       {
         const int ws0 = hf == 0 ? ps : Dims<H>::VL + row;
