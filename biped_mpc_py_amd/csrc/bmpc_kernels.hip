@@ -1018,6 +1018,30 @@ solve_body(const DevParams& P, const int B,
   bool piv_bad = false;                       // the last sweep met a pivot below PIV_MIN (uniform: every lane reads the same pivots)
   float sweep_reg = 0.f;                      // diagonal regularisation of the next sweep (the repeat after a breakdown)
   constexpr float PIV_REG = 3.0e-5f;
+  // The form of the symmetric sweep (the forms themselves: in factor(), at the sweep), stated here because the mat-vec of the
+  // iteration follows it: after a row-pair sweep V stays in the row-pair layout (ROWPAIR_MATVEC, at phase P4).
+#ifndef BMPC_STATIC_HN
+#define BMPC_STATIC_HN 54
+#endif
+#ifndef BMPC_ROWPAIR_HN
+#define BMPC_ROWPAIR_HN 30
+#endif
+#ifndef BMPC_ROWPAIR_MATVEC
+#define BMPC_ROWPAIR_MATVEC 1
+#endif
+  constexpr int PVS = Dims<H>::PVS;            // floats per published column (two-half layout + dump slots)
+  constexpr int QP = ((HN / 2 + 3) / 4) * 4;   // floats per quarter of a published column (row-pair form)
+  constexpr bool STATIC_SWEEP = HN <= BMPC_STATIC_HN;
+  constexpr bool ROWPAIR_SWEEP = STATIC_SWEEP && HN <= BMPC_ROWPAIR_HN && Dims<H>::WL && 4 * QP <= Dims<H>::VL &&
+                                 Dims<H>::VL + 32 + QP <= PVS;
+  // (and of the penalty moves, at the stopping test: a scheduled move's penalties formed once and kept over the reduction; the
+  //  h = 10 kernel is the one it was measured on; 0: formed twice, as before.  Stated here, not in the loop: a constant declared
+  //  in the loop body changed the register allocation of every horizon)
+#ifndef BMPC_RECLASSIFY_ONCE
+#define BMPC_RECLASSIFY_ONCE 1
+#endif
+  constexpr bool KEEP_MOVE = BMPC_RECLASSIFY_ONCE != 0 && H == 10;
+  constexpr bool ROWPAIR_MATVEC = ROWPAIR_SWEEP && BMPC_ROWPAIR_MATVEC != 0;   // (0: the mat-vec of round 24, instruction for instruction)
   auto factor = [&]() {
     if constexpr (PROF) t_mark = clock64();
 #ifdef BMPC_PROF_BLOCKS
@@ -1317,7 +1341,7 @@ solve_body(const DevParams& P, const int B,
     // Two pivots per barrier and LDS round trip instead of one; the update of the NEXT pair of pivot columns
     // is done first and published at once (into the other buffer), so that its round trip overlaps with the
     // rest of this step's updates.
-    constexpr int PVS = Dims<H>::PVS;            // floats per published column (two-half layout + dump slots)
+    // (PVS floats per published column: two-half layout + dump slots)
     // Up to h = 18 the sweep is unrolled over the HN / 2 steps of a column half and the register file does NOT rotate (round 6):
     // column k sits in register k mod HN of the lanes of half k / HN for good, every register index below is static, and the
     // half whose lanes publish is the only thing that changes from the first pass to the second.  The rotating form (below)
@@ -1326,10 +1350,7 @@ solve_body(const DevParams& P, const int B,
     // sweep 26.6 k -> 24.5 k cycles per factorisation at h = 10, kernel -2.3 % (configs 2, 4), -2.3 % at h = 16, -0.8 % at
     // h = 20 -- where the unrolled form spills 12 registers instead of 4 and the rotating one stays.  Same arithmetic in the
     // same order: iteration counts and results identical to the bit.
-#ifndef BMPC_STATIC_HN
-#define BMPC_STATIC_HN 54
-#endif
-    constexpr bool STATIC_SWEEP = HN <= BMPC_STATIC_HN;
+    // (STATIC_SWEEP, BMPC_STATIC_HN: in front of factor())
     // The row-pair form of the static sweep (round 24).  Above, a lane fetches the HN entries of both pivot rows of its column
     // half and every fetched entry feeds ONE FMA: 14 ds_read_b128 a step at h = 10, all of them broadcasts, and a broadcast costs
     // the LDS array what 64 distinct addresses cost -- the array, not the vector port, is the busier of the two resources the
@@ -1352,12 +1373,7 @@ solve_body(const DevParams& P, const int B,
     //     turned back into clones of the wave's last row behind it (one DPP move per register each way).
     // Selected for HN <= BMPC_ROWPAIR_HN (0: the form above for every horizon, the code of round 23 instruction for instruction)
     // where five steps fill a wave (the clone quad above) and the quarters fit the two-half vector: h = 10.
-#ifndef BMPC_ROWPAIR_HN
-#define BMPC_ROWPAIR_HN 30
-#endif
-    constexpr int QP = ((HN / 2 + 3) / 4) * 4;   // floats per quarter of a published column
-    constexpr bool ROWPAIR_SWEEP = STATIC_SWEEP && HN <= BMPC_ROWPAIR_HN && Dims<H>::WL && 4 * QP <= Dims<H>::VL &&
-                                   Dims<H>::VL + 32 + QP <= PVS;
+    // (ROWPAIR_SWEEP, QP floats per quarter of a published column: in front of factor())
     if constexpr (ROWPAIR_SWEEP) {
       const int p = (l >> 1) & 1;                // column parity held in the sweep
       auto quad_transpose = [&]() {              // {row, 2 columns} <-> {2 rows, column}: its own inverse
@@ -1479,9 +1495,13 @@ solve_body(const DevParams& P, const int B,
         }
         BMPC_DRAIN_LDS();                         // nothing in flight across the back edge (see sync_workgroup)
       }
-      quad_transpose();
+      // (ROWPAIR_MATVEC: V stays as it is -- the mat-vec of the iteration, its only reader, runs on this layout; the clone
+      //  lanes stay copies of the quad below them)
+      if constexpr (!ROWPAIR_MATVEC) {
+        quad_transpose();
 #pragma unroll
-      for (int i = 0; i < HN / 2; ++i) Vr[i] = f2{tail_pair_fill(Vr[i].x), tail_pair_fill(Vr[i].y)};
+        for (int i = 0; i < HN / 2; ++i) Vr[i] = f2{tail_pair_fill(Vr[i].x), tail_pair_fill(Vr[i].y)};
+      }
     } else if constexpr (STATIC_SWEEP) {
       const int ps = slot<H>(row);              // the own row's entry in a published column
       {
@@ -1887,7 +1907,12 @@ solve_body(const DevParams& P, const int B,
       for (int i = 0; i < 6; ++i) bsum = fmaf(lcol[i], f == 0 ? rj[0][i] : rj[1][i], bsum);
     }
     bsum += pair_swap(bsum);
-    sm.u.itv.beta[slot<H>(row)] = bsum * dsc;   // both lanes of the pair: same value (a + b == b + a)
+    if constexpr (ROWPAIR_MATVEC) {             // the quarter layout of a published pivot column: (half, column parity) x QP
+      const int rh = row >= HN ? row - HN : row;
+      sm.u.itv.beta[(2 * (row >= HN ? 1 : 0) + (rh & 1)) * QP + (rh >> 1)] = bsum * dsc;
+    } else {
+      sm.u.itv.beta[slot<H>(row)] = bsum * dsc;   // both lanes of the pair: same value (a + b == b + a)
+    }
     // the part of the step that does not need gamma (off the critical path, before the barrier):
     // t = N' r = r_0 - T' r_1 ;  null-space part of d: foot 0 gets Ka^-1 t, foot 1 gets -(T Ka^-1) t
     f2 ddk = {0.f, 0.f};
@@ -1904,11 +1929,44 @@ solve_body(const DevParams& P, const int B,
       for (int i = 0; i < 6; ++i) ddk = __builtin_elementwise_fma(kg[i], f2{tn[i], tn[i]}, ddk);
       if (f == 1) ddk = -ddk;
     }
+    if constexpr (ROWPAIR_MATVEC) BMPC_SCHED_BARRIER();   // (P3's tail stays in front of the barrier: P4 waits for nothing but beta)
     sync_workgroup();
     BMPC_STAMP(3)
     // --- P4: gamma = V beta over the own column half, summed over the pair   (Vr holds -S V S)
+    // After a row-pair sweep (ROWPAIR_MATVEC) V is still in the row-pair layout: lane (hf, p = (l >> 1) & 1) of an aligned quad
+    // holds Vr[i] = {V[rA][c], V[rA + 1][c]}, c = hf HN + 2 i + p, and beta lies in quarters (half, parity) like a published pivot
+    // column.  A lane fetches its quarter (QP / 4 ds_read_b128 instead of HNP / 4) and every entry feeds both rows of a packed
+    // FMA.  Same sums in the same order: below, a0.x, a0.y, a1.x, a1.y are four chains over the columns = 0, 1, 2, 3 (mod 4) of
+    // the half, ascending from zero; column 2 i + p is = p for even i and = 2 + p for odd i, so E[0] of lane p is the chain
+    // a0.{x, y}[p] and E[1] the chain a1.{x, y}[p], of both rows at once.  The quad exchange adds the other parity's chains,
+    // (a0.x + a0.y) + (a1.x + a1.y) for both rows (f32 addition commutes), the pair exchange the other half, and a lane keeps
+    // its own row's component.  The clone lanes, copies of the quad below them, come out with the wave's last row as before.
     float gown;
-    {
+    if constexpr (ROWPAIR_MATVEC) {
+      constexpr int NQ = QP / 4;
+      const f4* bsrc = reinterpret_cast<const f4*>(&sm.u.itv.beta[(2 * hf + ((l >> 1) & 1)) * QP]);
+      f4 b4[NQ];
+#pragma unroll
+      for (int jq = 0; jq < NQ; ++jq) b4[jq] = bsrc[jq];
+      BMPC_SCHED_BARRIER();
+      // (the quarter's padding is fetched with the rest: see keep_pad in the sweep)
+      if constexpr (HN / 2 % 4 != 0) BMPC_OPAQUE(b4[NQ - 1]);
+      auto bc = [](const f4& v, int k) -> f2 {   // entry k to both halves of the packed operand (op_sel), as in the sweep
+        if (k == 3) { f2 hi = v.zw; BMPC_PAIR(hi); return hi.yy; }
+        return k == 0 ? v.xx : (k == 1 ? v.yy : v.zz);
+      };
+      f2 E[2] = {{0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+      for (int i = 0; i < HN / 2; ++i) E[i & 1] = __builtin_elementwise_fma(Vr[i], bc(b4[i / 4], i % 4), E[i & 1]);
+      // (component by component: a DPP move folds into a one-float add, not into a packed one; the own row's component is
+      //  picked in front of the pair exchange -- both lanes of a pair pick the same -- so that one float crosses it)
+      const f2 S0 = {E[0].x + quad_swap(E[0].x), E[0].y + quad_swap(E[0].y)};
+      const f2 S1 = {E[1].x + quad_swap(E[1].x), E[1].y + quad_swap(E[1].y)};
+      const f2 both = S0 + S1;
+      float part = (row & 1) ? both.y : both.x;
+      part += pair_swap(part);
+      gown = -part * dsc;
+    } else {
       f2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
 #pragma unroll
       for (int q = 0; q < HN; q += 4) {
@@ -2086,11 +2144,18 @@ solve_body(const DevParams& P, const int B,
       nb = eqb ? P.rho_eq : (actb ? fminf(rvb * kapb, hib) : fmaxf(rvb / kapb, P.rho_lo));
       ng = actg ? fminf(rvg * kapg, hig) : fmaxf(rvg / kapg, P.rho_lo);
     };
+    // A scheduled move's new penalties are formed once and kept over the reduction (KEEP_MOVE): nothing they are formed from
+    // -- z, y, the penalties, the counters -- changes before the block behind it takes them.  Kept in LDS, eight bytes in a
+    // slot of the lane's own in the pivot buffers, which only factor() uses and the barriers of an iteration separate from
+    // here; the re-classification is ~60 vector instructions with two f32 divisions, 4.7 times per solve at h = 10.
+    // (KEEP_MOVE, BMPC_RECLASSIFY_ONCE: in front of factor())
+    static_assert(!KEEP_MOVE || 2 * NT <= 4 * PVS, "a slot per lane does not fit the pivot buffers");
     float chg = 0.f, nflip = 0.f;
     int act_now = 0;
     if (adapt_do) {
       float nb, ng;
       reclassify(nb, ng, act_now, true);
+      if constexpr (KEEP_MOVE) *(reinterpret_cast<f2*>(&sm.piv[0][0]) + l) = f2{nb, ng};
       chg = ((nb != rvb) | (ng != rvg)) ? 1.f : 0.f;
       // rows in another class than at the previous re-classification (the clones repeat a real lane: not counted)
       const int fl = act_now ^ prev_act;
@@ -2172,10 +2237,19 @@ solve_body(const DevParams& P, const int B,
         if (bad) { status = 2; break; }
         if (done) { status = 0; break; }
       }
-      if ((adapt_do && v5[4] > 0.f) || force_adapt) {   // (the new penalties are formed again rather than kept across the barrier)
+      if ((adapt_do && v5[4] > 0.f) || force_adapt) {   // (the new penalties: kept across the barrier where KEEP_MOVE, else formed again)
         float nb, ng;
         int a2;
-        reclassify(nb, ng, a2, adapt_do);
+        if constexpr (KEEP_MOVE) {
+          if (adapt_do) {                         // (uniform)
+            const f2 kept = *(reinterpret_cast<const f2*>(&sm.piv[0][0]) + l);
+            nb = kept.x; ng = kept.y;
+          } else {
+            reclassify(nb, ng, a2, false);
+          }
+        } else {
+          reclassify(nb, ng, a2, adapt_do);
+        }
         rvb = nb; rvg = ng;
         irvb = (RT)1 / (RT)rvb; irvg = (RT)1 / (RT)rvg;
         need_factor = true;
