@@ -30,6 +30,7 @@ EXPORTS = (
     "bmpc_plant_step_body", "bmpc_plant_step_body_device", "bmpc_simulate_body_device",
     "bmpc_plant_step_ground", "bmpc_plant_step_ground_device", "bmpc_simulate_ground_device",
     "bmpc_plant_rollout_samples", "bmpc_plant_rollout_samples_device",
+    "bmpc_plant_rollout_grad", "bmpc_plant_rollout_grad_device",
 )
 
 
@@ -115,6 +116,11 @@ class CRolloutOut(C.Structure):
     """`bmpc_rollout_out` of include/bmpc.h: per-sample values and per-instance reductions, each optional (NULL: not wanted)."""
     _fields_ = [(n, C.c_void_p) for n in ("cost", "score", "x_end", "foot_end", "x_traj", "first_fall", "max_tilt", "min_z", "first_slip",
                                            "slip_periods", "unloaded_periods", "mu_demand", "best", "n_valid", "weights", "u_mean", "ess")]
+
+
+class CRolloutGradOut(C.Structure):
+    """`bmpc_rollout_grad_out` of include/bmpc.h: the outputs of the roll-out gradient, each optional (NULL: not wanted)."""
+    _fields_ = [(n, C.c_void_p) for n in ("cost", "grad_u", "grad_x0", "grad_foot", "x_traj", "first_bad")]
 
 
 class BmpcError(RuntimeError):
@@ -242,6 +248,9 @@ def load():
                                      C.POINTER(CRolloutOut)]
     lib.bmpc_plant_rollout_samples.argtypes = rollout
     lib.bmpc_plant_rollout_samples_device.argtypes = rollout + [vp]
+    rollout_grad = [vp, ip, ip] + [vp] * 7 + [C.POINTER(CPlant), C.POINTER(CPlantBody), C.POINTER(CPlantGround), C.POINTER(CRolloutGradOut)]
+    lib.bmpc_plant_rollout_grad.argtypes = rollout_grad
+    lib.bmpc_plant_rollout_grad_device.argtypes = rollout_grad + [vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name != "bmpc_last_error":

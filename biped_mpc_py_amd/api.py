@@ -380,6 +380,43 @@ def _cost_function():
     return _Cost.apply
 
 
+_PLANT_COST_FUNCTION = None
+
+
+def _plant_cost_function():
+    """The `torch.autograd.Function` behind `BatchSolver.plant_cost_torch`, built on first use like `_cost_function`."""
+    global _PLANT_COST_FUNCTION
+    if _PLANT_COST_FUNCTION is not None:
+        return _PLANT_COST_FUNCTION.apply
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _PlantCost(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, solver, x_fb, foot, contact, controls, x_cmd, x_ref, push, opts):
+            want = ["cost", "grad_u"] + (["grad_x0"] if ctx.needs_input_grad[1] else []) + (["grad_foot"] if ctx.needs_input_grad[2] else [])
+            r = solver.plant_rollout_grad_device(x_fb.detach(), foot.detach(), contact, controls.detach().to(torch.float32).contiguous(),
+                                                 x_cmd=x_cmd, x_ref=x_ref, push=push, want=want, **opts)
+            ctx.dtypes = (x_fb.dtype, foot.dtype, controls.dtype)
+            ctx.has = ("grad_x0" in r, "grad_foot" in r)
+            ctx.save_for_backward(r["grad_u"], *[r[k] for k in ("grad_x0", "grad_foot") if k in r])
+            return r["cost"]
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_output):
+            grad_u, *rest = ctx.saved_tensors
+            grad_x0 = rest.pop(0) if ctx.has[0] else None
+            grad_foot = rest.pop(0) if ctx.has[1] else None
+            g_x = (grad_output[..., None] * grad_x0).sum(1).to(ctx.dtypes[0]) if grad_x0 is not None and ctx.needs_input_grad[1] else None
+            g_f = (grad_output[..., None] * grad_foot).sum(1).to(ctx.dtypes[1]) if grad_foot is not None and ctx.needs_input_grad[2] else None
+            g_u = (grad_output[..., None, None] * grad_u).to(ctx.dtypes[2]) if ctx.needs_input_grad[4] else None
+            return None, g_x, g_f, None, g_u, None, None, None, None
+
+    _PLANT_COST_FUNCTION = _PlantCost
+    return _PlantCost.apply
+
+
 class BatchSolver:
     """Owns one `bmpc_handle` (device memory + stream) for a fixed parameter block."""
 
@@ -1124,6 +1161,83 @@ class BatchSolver:
                                   w_unloaded, temperature, want)
         return self._rollout(_Device(self.device, x_fb.device, stream), B, S, opts, (x_fb, foot, contact, x_cmd, x_ref, push, controls),
                              body, ground)
+
+    # ---- the gradient of the plan roll-out (bmpc_plant_rollout_grad*) ------------------------------------
+    _ROLLOUT_GRAD_OUTPUTS = (("cost", "float64", ("B", "S")), ("grad_u", "float64", ("B", "S", "h", 12)),
+                             ("grad_x0", "float64", ("B", "S", 12)), ("grad_foot", "float64", ("B", "S", 6)),
+                             ("x_traj", "float32", ("B", "S", "h", 12)), ("first_bad", "int32", ("B", "S")))
+
+    @classmethod
+    def _rollout_grad_opts(cls, S, push_from, push_steps, integrator, substeps, move_feet, ground, want):
+        """(`bmpc_plant`, the names of the wanted outputs) from the keyword arguments of the gradient methods, checked as the library
+        checks them (ValueError).  `want` None: every output."""
+        plant = cls._plant(integrator, substeps, move_feet, push_from, push_steps)
+        cls._ground_mu(ground)
+        names = [k for k, _, _ in cls._ROLLOUT_GRAD_OUTPUTS]
+        want = names if want is None else list(want)
+        if not want or not set(want) <= set(names):
+            raise ValueError(f"want names at least one output among {names}")
+        if not 1 <= int(S) <= SAMPLES_MAX:
+            raise ValueError(f"controls must hold 1 <= S <= {SAMPLES_MAX} plans per instance")
+        return plant, want
+
+    def _rollout_grad(self, space, B, S, opts, inputs, body, ground):
+        """The roll-out gradient on exactly-typed arrays in `space`: `opts` as `_rollout_grad_opts` returns them, `inputs` in the
+        order of `_rollout_input_rows`.  The wanted outputs are allocated here; one call; returns their dict."""
+        plant, want = opts
+        args = space.ptrs(_rollout_input_rows, inputs, B, self.h, S)
+        cb, cg = self._body(space, body, B), self._ground(space, ground, B)
+        res = {k: space.empty(dtype, _shape(shape, B, self.h, S)) for k, dtype, shape in self._ROLLOUT_GRAD_OUTPUTS if k in want}
+        out = _lib.CRolloutGradOut(**{k: space.address(a) for k, a in res.items()})
+        if B == 0 and space.empty_is_null:      # (nothing to do, and an empty tensor has no address to hand over)
+            return res
+        _lib.check(getattr(self._lib, "bmpc_plant_rollout_grad" + space.suffix)(
+            self._h, B, S, *args, C.byref(plant), cb, cg, C.byref(out), *space.tail))
+        return res
+
+    def plant_rollout_grad(self, x_fb, foot, contact, controls, x_cmd=None, x_ref=None, push=None, push_from=0, push_steps=0,
+                           integrator="rk4", substeps=4, move_feet=True, body=None, ground=None, want=None):
+        """Which way each of S whole plans per instance should move on the rigid body (`bmpc_plant_rollout_grad`, include/bmpc.h):
+        the cost of `plant_rollout_samples` on the same arguments and its gradient, the discrete adjoint of that roll-out -- every
+        substep and stage of the plant step, the ground on the branch the forward pass took, the footholds landing legs take.  The
+        fp32 rounding of the stored states is the identity in the derivative; the references, the commands, the body, mu, the push
+        and the contact table are held fixed.  Returns a dict of NumPy arrays -- all of them, or those named in `want`: cost (B,S),
+        grad_u (B,S,h,12) = d cost / d controls, grad_x0 (B,S,12) = d cost / d x_fb, grad_foot (B,S,6) = d cost / d foot, float64;
+        x_traj (B,S,h,12) float32, the stored states; first_bad (B,S) int32: -1, or the period from which the plan's state is NaN
+        -- such a plan has NaN cost and gradients, and no other plan is touched."""
+        c32 = _samples_f32(controls, self.h)
+        B, S, h = c32.shape[0], c32.shape[1], self.h
+        opts = self._rollout_grad_opts(S, push_from, push_steps, integrator, substeps, move_feet, ground, want)
+        inputs = (_host_array("x_fb", x_fb, (B, 12)), _host_array("foot", foot, (B, 6)), _contact_u8(contact, B, h),
+                  _host_array("x_cmd", x_cmd, (B, 12), required=False), _host_array("x_ref", x_ref, (B, h, 12), required=False),
+                  _host_array("push", push, (B, 6), required=False), c32)
+        return self._rollout_grad(_Host(), B, S, opts, inputs, body, ground)
+
+    def plant_rollout_grad_device(self, x_fb, foot, contact, controls, x_cmd=None, x_ref=None, push=None, push_from=0, push_steps=0,
+                                  integrator="rk4", substeps=4, move_feet=True, body=None, ground=None, want=None, stream=None):
+        """`plant_rollout_grad` on CUDA(HIP) torch tensors of this solver's device (`bmpc_plant_rollout_grad_device`): float32 x_fb
+        (B,12), foot (B,6), controls (B,S,h,12), x_cmd (B,12), x_ref (B,h,12), push (B,6), uint8 contact (B,h,2); `body` and `ground`
+        of float64 device tensors as for `plant_step_device`.  The outputs -- all of them, or those named in `want` -- are allocated
+        here; one launch.  Asynchronous on `stream` (default: torch's current stream) unless the handle's scratch has to grow;
+        nothing crosses PCIe.  Returns the dict of output tensors."""
+        if x_fb.dim() != 2 or controls.dim() != 4:
+            raise ValueError(f"x_fb must have shape (B, 12) and controls (B, S, {self.h}, 12)")
+        B, S = x_fb.shape[0], int(controls.shape[1])
+        opts = self._rollout_grad_opts(S, push_from, push_steps, integrator, substeps, move_feet, ground, want)
+        return self._rollout_grad(_Device(self.device, x_fb.device, stream), B, S, opts,
+                                  (x_fb, foot, contact, x_cmd, x_ref, push, controls), body, ground)
+
+    def plant_cost_torch(self, x_fb, foot, contact, controls, x_cmd=None, x_ref=None, push=None, push_from=0, push_steps=0,
+                         integrator="rk4", substeps=4, move_feet=True, body=None, ground=None):
+        """`plant_rollout_samples`' cost as a differentiable torch value: float64 tensor (B,S) on the device, with gradients to
+        `controls` (B,S,h,12) in its dtype and, where they require one, to `x_fb` (B,12) and `foot` (B,6) -- the sums over an
+        instance's plans of grad_x0 and grad_foot, each scaled by the incoming gradient.  Every other argument is
+        non-differentiable.  The forward is ONE `bmpc_plant_rollout_grad_device` launch on torch's current stream, which leaves the
+        gradients behind; the backward scales them -- no second launch, no second derivative (`once_differentiable`).  What is
+        held fixed is what `plant_rollout_grad` holds fixed."""
+        return _plant_cost_function()(self, x_fb, foot, contact, controls, x_cmd, x_ref, push,
+                                      dict(push_from=push_from, push_steps=push_steps, integrator=integrator, substeps=substeps,
+                                           move_feet=move_feet, body=body, ground=ground))
 
     def last_kernel_ms(self):
         ms = C.c_float(-1.0)

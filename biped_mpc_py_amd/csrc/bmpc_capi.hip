@@ -10,6 +10,7 @@
 #include "bmpc_certify.hip"
 #include "bmpc_evaluate_samples.hip"
 #include "bmpc_plant_rollout.hip"
+#include "bmpc_plant_rollout_grad.hip"
 
 #include <chrono>
 #include <cmath>
@@ -245,6 +246,9 @@ struct bmpc_handle_s {
   DevBuf<float> ro_controls, ro_states;
   DevBuf<uint8_t> ro_contact;
   DevBuf<int32_t> ro_phase, ro_iters, ro_status, ro_order;
+  // roll-out gradient scratch (bmpc_plant_rollout_grad*): recorded states and footholds, substep states
+  DevBuf<float> rg_states, rg_feet;
+  DevBuf<double> rg_sub;
   const int32_t* order = nullptr;   // dispatch order of the next solves (bmpc_set_dispatch_order; roll-outs set their own)
   bool longest_first = true;        // roll-outs order each period's solve by the previous period's iteration counts
 };
@@ -1570,6 +1574,95 @@ int bmpc_plant_rollout_samples(bmpc_handle h, int B, const float* x_fb, const fl
   const bmpc_plant_ground d_ground = {d.at<double>(10)};
   const int rc = rollout_launch(h, B, d.at<float>(0), d.at<float>(1), d.at<uint8_t>(2), d.at<float>(3), d.at<float>(4), d.at<float>(5),
                               d.at<float>(6), o, body ? &d_body : nullptr, ground ? &d_ground : nullptr, *price, r.d, h->stream);
+  return rc != BMPC_OK ? rc : fetch(h, slots.s, r);
+}
+
+// ---- the gradient of the plant roll-out (bmpc_plant_rollout_grad.hip)
+
+// the outputs of bmpc_rollout_grad_out in its member order; a null descriptor gives all-null slots
+constexpr int N_RG = 6;
+static OutSlots<N_RG> rollout_grad_slots(const bmpc_rollout_grad_out* out, int S_) {
+  const bmpc_rollout_grad_out o = out ? *out : bmpc_rollout_grad_out{};
+  const size_t S = S_ >= 1 && S_ <= bmpc::SAMPLES_MAX ? (size_t)S_ : 1;
+  return {{{o.cost, {S, 0, 8}}, {o.grad_u, {0, 12 * S, 8}}, {o.grad_x0, {12 * S, 0, 8}}, {o.grad_foot, {6 * S, 0, 8}},
+           {o.x_traj, {0, 12 * S, 4}}, {o.first_bad, {S, 0, 4}}}};
+}
+
+// What both entries check, in the order of include/bmpc.h: an error code (< 0), BMPC_OK when there is nothing to do, 1 to go on.
+static int rollout_grad_check(bmpc_handle h, int B, int S, const float* x_fb, const float* foot, const uint8_t* contact,
+                              const float* controls, const bmpc_plant* plant, const bmpc_rollout_grad_out* out,
+                              const OutSlots<N_RG>& slots, bmpc_plant* o) {
+  if (S < 1 || S > bmpc::SAMPLES_MAX) return fail(BMPC_ERR_INVALID, "S = %d outside [1, %d]", S, bmpc::SAMPLES_MAX);
+  if (int rc = plant_opts(plant, o); rc != BMPC_OK) return rc;
+  if (!h) return fail(BMPC_ERR_INVALID, "null handle");
+  if (!x_fb || !foot || !contact || !controls) return fail(BMPC_ERR_INVALID, "x_fb, foot, contact and controls must be non-null");
+  if (!out) return fail(BMPC_ERR_INVALID, "null bmpc_rollout_grad_out");
+  bool any_out = false;
+  for (const OutSlot& s : slots.s) any_out = any_out || s.p;
+  if (!any_out) return fail(BMPC_ERR_INVALID, "bmpc_rollout_grad_out: at least one output must be non-null");
+  return check_batch(h, B);
+}
+
+// The launch, on device-addressable arrays; d: the slots of bmpc_rollout_grad_out in its order.  The scratch is made large enough
+// first: where that fails nothing is launched.
+static int rollout_grad_launch(bmpc_handle h, int B, int S, const float* x_fb, const float* foot, const uint8_t* contact,
+                               const float* x_cmd, const float* x_ref, const float* push, const float* controls, const bmpc_plant& o,
+                               const bmpc_plant_body* body, const bmpc_plant_ground* ground, void* const* d, hipStream_t st) {
+  const bmpc_params& p = h->params;
+  const size_t plans = (size_t)B * (size_t)S, H = (size_t)h->dev.h;
+  const bool grads = d[1] || d[2] || d[3];
+  if ((!d[4] && h->rg_states.ensure(plans * H * 12) != hipSuccess) || h->rg_feet.ensure(plans * H * 6) != hipSuccess ||
+      (grads && h->rg_sub.ensure(plans * (size_t)o.substeps * 6) != hipSuccess)) {
+    (void)hipGetLastError();
+    return fail(BMPC_ERR_ALLOC, "out of device memory for the scratch of %zu plans", plans);
+  }
+  bmpc::RolloutCost C;
+  for (int i = 0; i < 12; ++i) { C.Q[i] = p.Q[i]; C.R[i] = p.R[i]; C.x_cmd[i] = p.x_cmd[i]; }
+  const bool bd = has_body(body);
+  const bmpc::RolloutIn in = {x_fb, foot, contact, x_cmd, x_ref, push, controls, bd ? body->m : nullptr, bd ? body->I : nullptr,
+                              bd ? body->g : nullptr, ground ? ground->mu : nullptr, p.mu, ground ? 1 : 0, o.move_feet != 0 ? 1 : 0,
+                              o.push_from, o.push_steps};
+  const bmpc::RolloutGradOut out = {(double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (float*)d[4], (int32_t*)d[5]};
+  const bmpc::RolloutGradScratch W = {d[4] ? nullptr : h->rg_states.p, h->rg_feet.p, h->rg_sub.p, plans};
+  const size_t blocks = (plans + bmpc::RGRAD_NT - 1) / bmpc::RGRAD_NT;                 // (at most 2^24: B, S <= 65536)
+  hipLaunchKernelGGL(bmpc::plant_rollout_grad_kernel, dim3((unsigned)blocks), dim3(bmpc::RGRAD_NT), 0, st, plant_params(h),
+                     bmpc::plant_scheme(p.dt, o.integrator, o.substeps), C, in, out, W, B, S);
+  HIP_TRY(hipGetLastError());
+  return BMPC_OK;
+}
+
+int bmpc_plant_rollout_grad_device(bmpc_handle h, int B, int S, const float* x_fb, const float* foot, const uint8_t* contact,
+                                   const float* x_cmd, const float* x_ref, const float* push, const float* controls,
+                                   const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                                   const bmpc_rollout_grad_out* out, void* stream) {
+  const OutSlots<N_RG> slots = rollout_grad_slots(out, S);
+  bmpc_plant o;
+  if (int rc = rollout_grad_check(h, B, S, x_fb, foot, contact, controls, plant, out, slots, &o); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  void* d[N_RG];
+  for (int i = 0; i < N_RG; ++i) d[i] = slots.s[i].p;
+  return rollout_grad_launch(h, B, S, x_fb, foot, contact, x_cmd, x_ref, push, controls, o, body, ground, d, pick_stream(h, stream));
+}
+
+int bmpc_plant_rollout_grad(bmpc_handle h, int B, int S, const float* x_fb, const float* foot, const uint8_t* contact,
+                            const float* x_cmd, const float* x_ref, const float* push, const float* controls,
+                            const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                            const bmpc_rollout_grad_out* out) {
+  const OutSlots<N_RG> slots = rollout_grad_slots(out, S);
+  bmpc_plant o;
+  if (int rc = rollout_grad_check(h, B, S, x_fb, foot, contact, controls, plant, out, slots, &o); rc <= 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const InSlot in[11] = {{x_fb, IN[I_XFB].w}, {foot, IN[I_FOOT].w}, {contact, IN[I_CON].w}, {x_cmd, IN[I_XCMD].w}, {x_ref, IN[I_XREF].w},
+                         {push, W_WRENCH}, {controls, controls_width((size_t)S)}, {body ? body->m : nullptr, W_MASS},
+                         {body ? body->I : nullptr, W_INERTIA}, {body ? body->g : nullptr, W_GRAVITY},
+                         {ground ? ground->mu : nullptr, W_GROUND_MU}};
+  Slices<11> d; Slices<N_RG> r;
+  if (int rc = stage(h, B, in, &d, slots.s, &r); rc != BMPC_OK) return rc;
+  const bmpc_plant_body d_body = {d.at<double>(7), d.at<double>(8), d.at<double>(9)};
+  const bmpc_plant_ground d_ground = {d.at<double>(10)};
+  const int rc = rollout_grad_launch(h, B, S, d.at<float>(0), d.at<float>(1), d.at<uint8_t>(2), d.at<float>(3), d.at<float>(4),
+                                     d.at<float>(5), d.at<float>(6), o, body ? &d_body : nullptr, ground ? &d_ground : nullptr, r.d,
+                                     h->stream);
   return rc != BMPC_OK ? rc : fetch(h, slots.s, r);
 }
 

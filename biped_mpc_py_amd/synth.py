@@ -70,7 +70,7 @@ CONFIGS = {
 # the build, the source hash below and the emulation drivers read it (kernel_source_paths), so that an edit of any of these files
 # rebuilds all of them.  bmpc_capi.hip, the first, is the translation unit that includes the others.
 KERNEL_SOURCES = ("bmpc_capi.hip", "bmpc_kernels.hip", "bmpc_stage.hip", "bmpc_lowlevel.hip", "bmpc_evaluate.hip", "bmpc_evaluate_grad.hip",
-                  "bmpc_certify.hip", "bmpc_evaluate_samples.hip", "bmpc_plant.hip", "bmpc_plant_rollout.hip", "bmpc_model.hip",
+                  "bmpc_certify.hip", "bmpc_evaluate_samples.hip", "bmpc_plant.hip", "bmpc_plant_rollout.hip", "bmpc_plant_rollout_grad.hip", "bmpc_model.hip",
                   "bmpc_host_params.hpp", "bmpc_host_staging.hpp")
 
 

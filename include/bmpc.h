@@ -854,6 +854,60 @@ int bmpc_plant_rollout_samples(bmpc_handle h, int B, const float* x_fb, const fl
                                const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
                                const bmpc_rollout_price* price, const bmpc_rollout_out* out);
 
+/*
+ * Gradient of the plant roll-out (added under ABI 13 like the entries above: detect them by the symbol).  For plan (b, s) the
+ * forward pass is exactly the roll-out of bmpc_plant_rollout_samples as stated above -- the period loop, the ground in front of the
+ * step, the push window, the state rounded to fp32 and stored, landing by the contact table at the stored state, and
+ *   cost = sum_k sum_i Q_i (x_k,i - xr_k,i)^2 + R_i u_k,i^2   on the stored states and the COMMANDED controls --
+ * and the gradient is the discrete adjoint of that chain:
+ *   rounding   the fp32 rounding of a stored state, and of a scaled tangential force in the ground rule, is taken as the identity
+ *              in the derivative; the linearisation point is the stored (rounded) values
+ *   period     x_k = Phi(x_k-1, ua_k, r_k; c_k, w_k) is the plant step, differentiated exactly: every substep, every RK4 stage, the
+ *              rates through the three sincos, the plane rotations, I_b and I_b^-1, and the closed-form p, v updates
+ *   ground     ua_k = T(u_k), differentiated on the branch the forward pass took: a swing leg or an unloaded stance leg has a zero
+ *              Jacobian block, a loaded leg inside the cone the identity, a slipping leg the Jacobian of
+ *              (fx, fy) mu fz / sqrt(fx^2 + fy^2) with respect to (fx, fy, fz); moments pass.  The R_i u^2 term always sees the command
+ *   footholds  are part of the chain: Phi depends on r_k, and a leg that lands after period k takes the target, which is affine in
+ *              x_k[3], x_k[9] and x_k[4], x_k[10].  A foothold costate (6 values) runs backwards, collects (dPhi/dr)' lambda each
+ *              period, is folded into lambda_k at a landing through the target's coefficients with that leg's part zeroed, and what is
+ *              left at k = 0 is grad_foot.  With move_feet == 0 nothing is folded
+ *   held fixed (as bmpc_evaluate_grad does): the reference rows (generated rows depend on x_fb: that dependence is not
+ *              differentiated), the commands, the body, mu, the push and the contact table.  The outcome and the slip counters are
+ *              not differentiated and are not outputs here.
+ * Outputs per plan, each optional, at least one wanted: cost [B][S] fp64; grad_u [B][S][h][12] fp64 = d cost / d controls;
+ * grad_x0 [B][S][12] fp64 = d cost / d x_fb; grad_foot [B][S][6] fp64 = d cost / d foot; x_traj [B][S][h][12] fp32, the stored
+ * states; first_bad [B][S] int32: -1, or the period from which the plan's state is NaN.  A plan that is bad by
+ * bmpc_plant_rollout_samples' rules has cost and every gradient entry NaN; no other plan is touched.
+ * Exactly: an entry of grad_u that the plant never sees -- a swing leg's six values in period k and, with a ground, an unloaded
+ * stance leg's -- is the fp64 product 2.0 * R_i * (double)u, in that order; grad_u[h-1] depends on
+ * lambda_h-1 = 2 Q (x_h-1 - xr_h-1) alone.
+ *   bmpc_plant_rollout_grad_device   DEVICE pointers (members of body, ground and out included), asynchronous on `stream` unless the
+ *                                    handle's scratch has to grow
+ *   bmpc_plant_rollout_grad          HOST pointers, synchronous (staged through the handle's own stream)
+ * One launch, one thread per plan.  The recorded states (where x_traj is not wanted), the footholds every period started with and
+ * the substep states of the period being transposed live in scratch on the handle, allocated on demand:
+ * B S (4 (12 h + 6 h) + 48 substeps) bytes at most; if it cannot be allocated the entry returns BMPC_ERR_ALLOC with nothing launched.
+ * Checked before a device is touched, each BMPC_ERR_INVALID, in this order: S outside [1, 65536]; the plant block as for
+ * bmpc_simulate_device; a NULL handle, x_fb, foot, contact, controls or `out`; all outputs NULL; B outside [0, max_batch].  B = 0
+ * succeeds.  The handle's parameter block is read (bmpc_set_params takes effect) and none of its per-solve state is touched.
+ */
+typedef struct bmpc_rollout_grad_out {   /* each NULL = not wanted; at least one non-NULL */
+  double*  cost;              /* [B][S]        */
+  double*  grad_u;            /* [B][S][h][12] */
+  double*  grad_x0;           /* [B][S][12]    */
+  double*  grad_foot;         /* [B][S][6]     */
+  float*   x_traj;            /* [B][S][h][12] */
+  int32_t* first_bad;         /* [B][S]        */
+} bmpc_rollout_grad_out;
+int bmpc_plant_rollout_grad_device(bmpc_handle h, int B, int S, const float* x_fb, const float* foot, const uint8_t* contact,
+                                   const float* x_cmd, const float* x_ref, const float* push, const float* controls,
+                                   const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                                   const bmpc_rollout_grad_out* out, void* stream);
+int bmpc_plant_rollout_grad(bmpc_handle h, int B, int S, const float* x_fb, const float* foot, const uint8_t* contact,
+                            const float* x_cmd, const float* x_ref, const float* push, const float* controls,
+                            const bmpc_plant* plant, const bmpc_plant_body* body, const bmpc_plant_ground* ground,
+                            const bmpc_rollout_grad_out* out);
+
 /* Diagnostics: when device_buf (DEVICE pointer, [max_batch][16] int64) is non-NULL every later solve
  * writes per-instance shader-clock stamps {setup, block algebra, dense sweeps, total, iters,
  * factorisations, -, -, iteration phases P0..P5, stop test + adaptation, -}; NULL switches it off
